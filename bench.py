@@ -12,10 +12,16 @@ sharded (independent problems, no data-path collective): by defau
 of its own.  Shards come from the same counter-based generator at the shard's first
 trajectory index, so the union of the shards is the one-GPU batch.
 
-Prints ONE JSON line on rank 0 (contract in the task description), with a `roofline`
-object for the Riccati kernel (fp64 compute roofline: algorithmic flops per launch ÷ the
-kernel's own HIP-event-timed duration on the launch stream) and a `cpu_baseline` object
-(the CPU oracle — a restatement of the reference path — timed on a bounded sample).
+Prints ONE JSON line on rank 0, with a `roofline` object for the Riccati kernel (fp64
+compute roofline: algorithmic flops per launch ÷ the timed steps' own HIP-event-timed
+duration on the launch stream — arithmetic on the timed run, no run of its own).
+
+A plain run sets up, warms up, times `--steps` steps, writes `--dump-outputs DIR` if asked
+and prints the line.  `--full` adds what takes work of its own and fills the line's
+`check`, `cpu_baseline` and `gather` fields (null in a plain run): the whole-batch output
+scans, the sampled parity against the CPU oracle, the `cpu_baseline` object (the CPU
+oracle — a restatement of the reference path — timed on a bounded sample) and, for N > 1,
+the timed gather to rank 0.
 """
 from __future__ import annotations
 
@@ -373,6 +379,40 @@ def nonfinite_count(out, keys):
     return int(sum(int((~torch.isfinite(out[k])).sum().item()) for k in keys if k in out))
 
 
+DUMP_BUDGET_BYTES = 48 << 20    # --dump-outputs: all files together stay under 64 MB
+DUMP_SAMPLE_SEED = 20260104
+
+
+def dump_outputs(path, arrays, bt, soa=False):
+    """--dump-outputs: write what the timed path's last step left in its output buffers as
+    path/<name>.npy, one row per trajectory.  Floating-point arrays keep their precision
+    (float32 / float64); integer status arrays are written as float64.  Past DUMP_BUDGET_BYTES
+    the rows are a fixed seeded sample of the batch's trajectories (sorted, the same rows in
+    every array and every run), otherwise the whole batch.  soa: the buffers are
+    [element][batch] (KKT ABI layout 1).  Returns what was written, for the result line."""
+    import numpy as np
+    import torch
+
+    def out_dtype(v):
+        return v.dtype if v.dtype in (torch.float32, torch.float64) else torch.float64
+
+    per_traj = sum(v.numel() // bt * torch.empty(0, dtype=out_dtype(v)).element_size()
+                   for v in arrays.values())
+    k = int(max(1, min(bt, DUMP_BUDGET_BYTES // max(per_traj, 1))))
+    idx = None
+    if k < bt:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(bt, size=k, replace=False))
+    os.makedirs(path, exist_ok=True)
+    for name, v in arrays.items():
+        rows = v.view(-1, bt).t() if soa else v.view(bt, -1)
+        if idx is not None:
+            rows = rows.index_select(0, torch.from_numpy(idx).to(v.device))
+        np.save(os.path.join(path, name + ".npy"),
+                np.ascontiguousarray(rows.to(out_dtype(v)).cpu().numpy()))
+    return {"dir": path, "arrays": sorted(arrays), "trajectories": k, "of": bt,
+            "sample": None if idx is None else f"numpy default_rng({DUMP_SAMPLE_SEED}).choice, sorted"}
+
+
 def _rank_main(argv):
     """Entry of a rank spawned by main() (lqrx.shard.spawn_ranks sets RANK / WORLD_SIZE)."""
     return main(argv)
@@ -417,7 +457,16 @@ def main(argv=None):
                     help="launcher + partition + timing scaffolding only, on the CPU (gloo), no solve")
     ap.add_argument("--dtype", choices=["f64", "f32"], default="f64")
     ap.add_argument("--seed", type=int, default=20260104)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: the whole-batch output scans (non-finite values, "
+                         "info), the sampled parity against the CPU oracle, the cpu_baseline and, "
+                         "for N > 1, the timed info + P_1 gather to rank 0; a plain run leaves "
+                         "these fields null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's output arrays (a fixed seeded "
+                         "sample of trajectories when they exceed 48 MiB) as DIR/<name>.npy; one GPU")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the cpu_baseline")
     ap.add_argument("--tv", action="store_true",
                     help="dp: time-varying problem (per-knot A_k, B_k, Q_k, R_k; knot_stride 1, "
                          "SURVEY §8(f) rank 1); default batch 16384 (65536 would need 376 GB)")
@@ -460,6 +509,10 @@ def main(argv=None):
     if args.graph and args.workload == "sqp":
         ap.error("--graph: the sqp workload reads its active count back to the host every loop pass "
                  "(lqrx_sqp.hip), which a HIP graph capture cannot contain; use dp, cartpole, kkt or ls")
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs writes one GPU's outputs; use --gpus 1")
+    if not args.full:
+        args.no_cpu_baseline = True
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         # no launcher: spawn one rank per GPU now, before this process touches a GPU
@@ -641,15 +694,24 @@ def main(argv=None):
     wall = SH.timed_steps(step, args.steps, args.warmup, sync, world,
                           on_start=lambda: ev0.record(stream), on_stop=lambda: ev1.record(stream))
     kern_ms = ev0.elapsed_time(ev1) / args.steps       # stream-timed launch duration
-    bad = int((out["info"] != 0).sum().item()) if args.workload != "sqp" else \
-        int((out["info"] == 2).sum().item())                  # SQP: line-search failures
-    # output checks, outside the timed region: the whole batch scanned on the device for
-    # non-finite values; a strided sample compared with the CPU oracle (rank 0)
-    nonfinite = nonfinite_count(out if args.workload != "sqp" else t,
-                                ("K", "P", "X", "U", "d", "p", "dz", "lam", "Z"))
-    nonfinite, bad = SH.sum_over_ranks([nonfinite, bad], world, cdev)
-    sampled = None
-    if rank == 0 and args.workload in ("dp", "cartpole", "kkt"):
+    dumped = None
+    if args.dump_outputs:
+        names = {"ls": ("U", "X", "info"), "kkt": ("dz", "lam", "info"),
+                 "sqp": ("Z", "lam", "iters", "status")}.get(args.workload, ("K", "P", "X", "U", "d", "p", "info"))
+        src = t if args.workload == "sqp" else out
+        dumped = dump_outputs(args.dump_outputs, {k: src[k] for k in names if k in src}, bt,
+                              soa=args.workload == "kkt" and args.kkt_structure != "dense"
+                              and bool(args.kkt_layout))
+    nonfinite = bad = sampled = None
+    if args.full:
+        bad = int((out["info"] != 0).sum().item()) if args.workload != "sqp" else \
+            int((out["info"] == 2).sum().item())                  # SQP: line-search failures
+        # output checks, outside the timed region: the whole batch scanned on the device for
+        # non-finite values; a strided sample compared with the CPU oracle (rank 0)
+        nonfinite = nonfinite_count(out if args.workload != "sqp" else t,
+                                    ("K", "P", "X", "U", "d", "p", "dz", "lam", "Z"))
+        nonfinite, bad = SH.sum_over_ranks([nonfinite, bad], world, cdev)
+    if args.full and rank == 0 and args.workload in ("dp", "cartpole", "kkt"):
         thr = max(1, min(16, os.cpu_count() or 1))
         if args.workload == "kkt" and args.kkt_structure == "dense":
             sampled = check_kkt_dense_sample(out, t, st, _sample_index(bt, 4), bt, thr, f64)
@@ -664,7 +726,7 @@ def main(argv=None):
     # final gather, timed separately from the solve: info + P_1 of every
     # shard to rank 0 over RCCL (grouped send/recv); K stays sharded
     gather = None
-    if world > 1 and args.workload in ("dp", "cartpole") and not args.no_gather:
+    if args.full and world > 1 and args.workload in ("dp", "cartpole") and not args.no_gather:
         # a failure here propagates: the rank exits non-zero (spawn_ranks / the launcher
         # report it) instead of printing a line with the error folded into a field
         fields = {"info": out["info"], "P": out["P"]}
@@ -926,9 +988,13 @@ def main(argv=None):
                        "hip_graph": bool(args.graph)},
             "roofline": roof,
             "cpu_baseline": cpu,
-            "check": {"nonfinite": nonfinite, "info_nonzero": bad, "sampled_parity": sampled},
+            "check": {"nonfinite": nonfinite, "info_nonzero": bad, "sampled_parity": sampled}
+            if args.full else None,
             "gather": gather,
+            "full": bool(args.full),
         }
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         if gather is not None and "ms" in gather:
             line["value_solve_plus_gather"] = total / (wall + gather["ms"] * 1e-3)
         try:   # build provenance: the library's compiled-in source hash vs this tree's

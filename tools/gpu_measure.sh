@@ -73,7 +73,7 @@ kt_pass() {
     trim
 }
 bench_line() {
-    timeout -k 10 600 python -u bench.py "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; return 2; }
+    timeout -k 10 600 python -u bench.py --full "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; return 2; }
     cut -c1-240 "$OUT/bench.json"
 }
 

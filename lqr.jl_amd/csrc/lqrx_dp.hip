@@ -157,7 +157,13 @@ __device__ __forceinline__ bool aug_ldl_forward(T *aug, int lane)
 }
 
 // Newton–Schulz refinement of X ≈ E⁻¹ (E SPD, MT×MT tiles), warm-started from the previous
-// knot's inverse.  One step: R = I − EᵀX (4·MT³ MFMAs, neg-A with C = I), X ← X + XᵀR.
+// knot's inverse.  One step: R = I − EᵀX (4·MT³ MFMAs, neg-A with C = I), then the update
+// X += XᵀR done IN PLACE: mma_tn(X, X, R) has its accumulator alias its M operand, so the
+// MFMA of k-slice s reads, as rows 4s… of "X", a tile that the slices before it have already
+// added to — a Gauss–Seidel-like sweep X ← X + Σ_s X⁽ˢ⁾[s]ᵀR[s] (X⁽ˢ⁾: X after slices < s), not
+// the out-of-place X + XᵀR.  Each slice's correction differs from the out-of-place one by
+// O(‖X‖‖R‖²), so the step still contracts quadratically; every slice is a true MFMA→MFMA
+// dependency on the one before it (the waits that PnShadow's chunks, below, are issued into).
 // Returns true once the step just taken is converged to working precision: with
 // ρ = 16·MT·max|R| ≥ ‖R‖∞ the new residual is ≤ cond(E)·ρ², so ρ ≤ tol (1e-11 in fp64:
 // cond·1e-22, far below the rounding floor) accepts.  Not converged after `it` steps
@@ -179,34 +185,163 @@ __device__ __forceinline__ double key_bound(int k, double) { return __hiloint2do
 __device__ __forceinline__ int mag_key(float v) { return __float_as_int(v) & 0x7fffffff; }
 __device__ __forceinline__ float key_bound(int k, float) { return __int_as_float(k); }
 
+// The acceptance tests on ρ = 16·MT·key_bound(key) as integer compares on the key itself.
+// 16·MT is a power of two, so the product is exact (or overflows to +inf, above every
+// tolerance, as its key is above every threshold) and  ρ ≤ tol ⇔ key_bound(key) ≤ t,
+// ρ < 1 ⇔ key_bound(key) < 1/(16·MT),  with t = tol/(16·MT), an exact quotient.
+//   fp32: key_bound(key) is the float whose bits are key, and non-negative floats order as
+//         their bits, so  key_bound(key) ≤ t ⇔ key ≤ bits(t).
+//   fp64: key_bound(key) is the LARGEST double with high word key.  With (h, l) the words of
+//         t: key < h ⇒ below t;  key > h ⇒ above t;  key = h ⇒ (h, 0xffffffff) ≤ (h, l) only if
+//         l = 0xffffffff.  So  key_bound(key) ≤ t ⇔ key ≤ h − (l ≠ 0xffffffff).
+//   ρ < 1: 1/(16·MT) has a zero low word / mantissa, so  key_bound(key) < it ⇔ key < its key
+//         (fp64: (h, 0xffffffff) is above (h, 0);  fp32: equal bits are not below).
+//   NaN:  every NaN key — and the fp64 +inf key, whose bound (0x7ff00000, 0xffffffff) is a
+//         NaN — is above every threshold here: not accepted, not contracting, as before.
+// tests/test_ns_keys.py restates both decisions on the host and compares them key by key.
+template <typename T, int MT> struct NsKey;
+template <int MT> struct NsKey<double, MT> {
+    static constexpr int le(double t)
+    {
+        const unsigned long long b = __builtin_bit_cast(unsigned long long, t);
+        return (int)(b >> 32) - ((b & 0xffffffffull) != 0xffffffffull ? 1 : 0);
+    }
+    static constexpr int v = le(NsTol<double>::v / (16 * MT));
+    static constexpr int one_step = le(NsTol<double>::one_step / (16 * MT));
+    static constexpr int below_one = (int)(__builtin_bit_cast(unsigned long long, 1.0 / (16 * MT)) >> 32) - 1;
+};
+template <int MT> struct NsKey<float, MT> {
+    static constexpr int v = __builtin_bit_cast(int, NsTol<float>::v / (16 * MT));
+    static constexpr int one_step = __builtin_bit_cast(int, NsTol<float>::one_step / (16 * MT));
+    static constexpr int below_one = __builtin_bit_cast(int, 1.0f / (16 * MT)) - 1;
+};
+
+// Work for the iteration's shadow: MFMAs that do not depend on the solve, handed to ns_refine
+// in numbered chunks.  The iteration is one serial chain — the residual's MFMAs feed the test,
+// every slice of the in-place update feeds the next, the update feeds K = XᵀG — and a one-wave
+// workgroup has nothing else of its own to issue while a result is in flight.  ns_refine issues
+// chunk 0 behind the first residual (before its test), chunks 1 … 4·MT behind the 4·MT k-slices
+// of the first update, chunk 4·MT + 1 behind the second residual; the caller issues whatever
+// the path taken did not reach (rest()).  NsNoShadow: nothing to issue.
+struct NsNoShadow {
+    template <int C> __device__ __forceinline__ void chunk() const {}
+};
+// the K-independent part of P_: Pn += AᵀPA (lower tiles), mma_tn_lower's MFMAs in its order,
+// cut into NCH = 4·MT + 2 chunks (per accumulator the MFMA order is mma_tn_lower's: same bits)
+template <typename T, int NT, int MT> struct PnShadow {
+    using acc = typename Tile<T>::acc;
+    static constexpr int NCH = 4 * MT + 2, TOT = mma_tn_lower_count<T, NT, NT>();
+    static constexpr int CH = (TOT + NCH - 1) / NCH;
+    acc (&Pn)[NT][NT];
+    const acc (&At)[NT][NT];
+    const acc (&PA)[NT][NT];
+    template <int C> __device__ __forceinline__ void chunk() const
+    {
+        // pinned: the scheduler must not move the chunk off the wait it is there to cover
+        __builtin_amdgcn_sched_barrier(0);
+        mma_tn_lower_range<T, NT, NT, C * CH, (C + 1) * CH>(Pn, At, PA);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    // chunks [B, E) unpinned
+    template <int B, int E> __device__ __forceinline__ void range() const
+    {
+        mma_tn_lower_range<T, NT, NT, B * CH, E * CH>(Pn, At, PA);
+    }
+    // the chunks ns_refine did not issue: `done` is 0 (not called), 1, 4·MT + 1 or NCH
+    __device__ __forceinline__ void rest(int done) const
+    {
+        if (done < 1) range<0, 1>();
+        if (done < 4 * MT + 1) range<1, 4 * MT + 1>();
+        if (done < NCH) range<4 * MT + 1, NCH>();
+    }
+};
+
+// k-slice S (k-tile S / 4, register S % 4) of mma_tn(X, X, R) and the slices after it, chunk
+// 1 + S behind each
+template <typename T, int MT, int S, typename F>
+__device__ __forceinline__ void ns_update_shadowed(typename Tile<T>::acc (&X)[MT][MT],
+                                                   const typename Tile<T>::acc (&R)[MT][MT], const F &shadow)
+{
+    constexpr int k = S / 4, r = S % 4;
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < MT; ++j) X[i][j] = Tile<T>::mma(X[k][i][r], R[k][j][r], X[i][j]);
+    shadow.template chunk<1 + S>();
+    if constexpr (S + 1 < 4 * MT) ns_update_shadowed<T, MT, S + 1>(X, R, shadow);
+}
+
+// one round; ROUND 0 / 1 / 2: first, second, later.  Returns 0 to go on, 1 accepted, 2 rejected.
+template <typename T, int MT, int ROUND, typename F>
+__device__ __forceinline__ int ns_round(typename Tile<T>::acc (&X)[MT][MT],
+                                        const typename Tile<T>::acc (&E)[MT][MT],
+                                        const typename Tile<T>::acc (&Id)[MT][MT], const F &shadow, int &done)
+{
+    using acc = typename Tile<T>::acc;
+    acc R[MT][MT];
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < MT; ++j) R[i][j] = Id[i][j];
+    mma_tn<T, MT, MT, MT, true>(R, E, X);                       // R = I − EᵀX
+    if constexpr (ROUND == 0) {
+        shadow.template chunk<0>();
+        done = 1;
+    }
+    if constexpr (ROUND == 1) {
+        shadow.template chunk<4 * MT + 1>();
+        done = 4 * MT + 2;
+    }
+    int key = 0;
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < MT; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) key = max(key, mag_key(R[i][j][r]));
+    // uniform (SGPR) key of the residual bound ρ = 16·MT·key_bound(key) ≥ ‖R‖∞ (a NaN key
+    // if any element is NaN); the tests on ρ are integer compares on the key (NsKey)
+    key = wave_max_uniform_i(key);
+    if (key <= NsKey<T, MT>::v) return 1;                       // ρ ≤ v: X already at working precision
+    if (key > NsKey<T, MT>::below_one) return 2;                // !(ρ < 1), no contraction (or NaN): exact sweep
+    if constexpr (ROUND == 0) {
+        // X += XᵀR in place (see above), mma_tn's MFMAs in its order, a chunk behind each k-slice
+        ns_update_shadowed<T, MT, 0>(X, R, shadow);
+        done = 4 * MT + 1;
+    } else {
+        mma_tn<T, MT, MT, MT>(X, X, R);                         // X += XᵀR, in place (see above)
+    }
+    if (key <= NsKey<T, MT>::one_step) return 1;                // ρ ≤ one_step: new residual ≤ cond·ρ² ≪ eps
+    return 0;
+}
+
+template <typename T, int MT, typename F>
+__device__ __forceinline__ bool ns_refine(typename Tile<T>::acc (&X)[MT][MT],
+                                          const typename Tile<T>::acc (&E)[MT][MT],
+                                          const typename Tile<T>::acc (&Id)[MT][MT], const F &shadow, int &done)
+{
+    static_assert(NsTol<T>::it >= 2, "two peeled rounds");
+    int s = ns_round<T, MT, 0>(X, E, Id, shadow, done);
+    if (s) return s == 1;
+    s = ns_round<T, MT, 1>(X, E, Id, shadow, done);
+    if (s) return s == 1;
+    for (int it = 2; it < NsTol<T>::it; ++it) {
+        s = ns_round<T, MT, 2>(X, E, Id, shadow, done);
+        if (s) return s == 1;
+    }
+    return false;
+}
 template <typename T, int MT>
 __device__ __forceinline__ bool ns_refine(typename Tile<T>::acc (&X)[MT][MT],
                                           const typename Tile<T>::acc (&E)[MT][MT],
                                           const typename Tile<T>::acc (&Id)[MT][MT], int lane)
 {
-    using acc = typename Tile<T>::acc;
-    for (int it = 0; it < NsTol<T>::it; ++it) {
-        acc R[MT][MT];
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int j = 0; j < MT; ++j) R[i][j] = Id[i][j];
-        mma_tn<T, MT, MT, MT, true>(R, E, X);                   // R = I − EᵀX
-        int key = 0;
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int j = 0; j < MT; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) key = max(key, mag_key(R[i][j][r]));
-        // uniform (SGPR) residual bound ρ ≥ ‖R‖∞ (NaN if any element is NaN)
-        const T rho = (T)(16 * MT) * key_bound(wave_max_uniform_i(key), (T)0);
-        if (rho <= NsTol<T>::v) return true;                    // X already at working precision
-        if (!(rho < (T)1)) return false;                        // no contraction (or NaN): exact sweep
-        mma_tn<T, MT, MT, MT>(X, X, R);                         // X ← X + XᵀR
-        if (rho <= NsTol<T>::one_step) return true;             // new residual ≤ cond·ρ² ≪ eps
-    }
     (void)lane;
+    int done = 0;
+    for (int it = 0; it < NsTol<T>::it; ++it) {
+        const int s = ns_round<T, MT, 2>(X, E, Id, NsNoShadow{}, done);
+        if (s) return s == 1;
+    }
     return false;
 }
 
@@ -607,6 +742,8 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
     using acc = typename Tile<T>::acc;
     constexpr int MP = C::MP, CS = C::CS;
     constexpr bool TV = (VAR & VAR_TV) != 0, LIN = (VAR & VAR_LIN) != 0;
+    // Q + AᵀPA in the shadow of the Newton–Schulz chain (PnShadow): time-invariant A only
+    constexpr bool SHADOW = !TV && (VAR & (VAR_NOSOLVE | VAR_SWEEPONLY)) == 0;
     constexpr int NP = C::NP;
     __shared__ T lds[C::LDS_ELEMS];
     // p (NP), then w / d (MP); time-invariant q (NP), r (MP) images after them
@@ -681,6 +818,13 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
                 Xi[i][j][r] = (T)0;
                 Xp[i][j][r] = (T)0;
             }
+    // per-trajectory values of the knot loop, formed once: the symmetrize's diagonal-tile LDS
+    // indices (kept opaque so that they stay in registers and are not re-derived per knot)
+    const bool ns_off = a.ns_off != 0;
+    int didx[4];
+    symmetrize_diag_index<T, NT>(didx, lane);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) asm volatile("" : "+v"(didx[r]));
 
     for (int k = N - 1; k >= 1; --k) { // :61
         acc PB[NT][MT], E[MT][MT], PA[NT][NT], G[MT][NT], Pn[NT][NT];
@@ -725,7 +869,12 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
         mma_tn<T, NT, MT, MT>(E, Bt, PB);                          // :39 E = R + B'PB
         tiles_zero<T, MT, NT>(G);
         mma_tn<T, NT, MT, NT>(G, Bt, PA);                          // :41 K = B'PA
-        mma_tn_lower<T, NT, NT>(Pn, At, PA);                       // :51 Q + A'PA (lower)
+        // :51 Q + A'PA (lower): independent of the solve.  Time-invariant A: issued in chunks in
+        // the shadow of the Newton–Schulz chain below (PnShadow); time-varying: here, before
+        // A_k leaves the tiles.
+        const PnShadow<T, NT, MT> pn_shadow{Pn, At, PA};
+        int pn_done = 0;
+        if constexpr (!SHADOW) mma_tn_lower<T, NT, NT>(Pn, At, PA);
         // linear terms, first half (time-varying: before A_k, B_k leave the tiles; time-
         // invariant: after the solve, where fewer registers are live): w = r + Bᵀp, Aᵀp partials
         T w[LIN ? MT : 1], ap[LIN ? NT : 1];
@@ -778,13 +927,17 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
                             X0[i][j] = Xi[i][j];
                             Xi[i][j] = (T)2 * Xi[i][j] - Xp[i][j];   // = X_{k+1} at k = N−2 (Xp = Xi there)
                         }
-                    have = !a.ns_off && ns_refine<T, MT>(Xi, E, Id, lane);
+                    if constexpr (SHADOW) have = !ns_off && ns_refine<T, MT>(Xi, E, Id, pn_shadow, pn_done);
+                    else have = !ns_off && ns_refine<T, MT>(Xi, E, Id, lane);
 #pragma unroll
                     for (int i = 0; i < MT; ++i)
 #pragma unroll
                         for (int j = 0; j < MT; ++j) Xp[i][j] = X0[i][j];
                 }
             }
+            // what the path taken left of Q + A'PA (all of it ahead of an exact sweep that ran
+            // no iteration)
+            if constexpr (SHADOW) pn_shadow.rest(pn_done);
             if (!have) {
                 tiles_to_lds<T, MT, MT>(E, lds, CS, lane);
                 __syncthreads();
@@ -862,7 +1015,7 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
             }
         }
         mma_tn_lower<T, MT, NT, true>(Pn, G, Kt);                  // :50-51 − GᵀK (= APB K)
-        tiles_symmetrize_lower<T, NT>(Pn, lds, lane);              // P_ exactly symmetric
+        tiles_symmetrize_lower<T, NT>(Pn, lds, didx, lane);        // P_ exactly symmetric
 #pragma unroll
         for (int i = 0; i < NT; ++i)
 #pragma unroll

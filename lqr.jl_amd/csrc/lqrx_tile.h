@@ -177,6 +177,28 @@ __device__ __forceinline__ void mma_tn_lower(typename Tile<T>::acc (&D)[NT][NT],
                                   : Tile<T>::mma(M[k][i][r], Y[k][j][r], D[i][j]);
 }
 
+// MFMAs [BEG, END) of mma_tn_lower's sequence (numbered in its issue order), so that one
+// product can be issued in pieces; pieces issued in ascending order give every accumulator
+// the same MFMAs in the same order as mma_tn_lower — the same bits.
+template <typename T, int KT, int NT>
+constexpr int mma_tn_lower_count() { return KT * 4 * (NT * (NT + 1) / 2); }
+template <typename T, int KT, int NT, int BEG, int END>
+__device__ __forceinline__ void mma_tn_lower_range(typename Tile<T>::acc (&D)[NT][NT],
+                                                   const typename Tile<T>::acc (&M)[KT][NT],
+                                                   const typename Tile<T>::acc (&Y)[KT][NT])
+{
+    int idx = 0;
+#pragma unroll
+    for (int k = 0; k < KT; ++k)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int i = 0; i < NT; ++i)
+#pragma unroll
+                for (int j = 0; j <= i; ++j, ++idx)
+                    if (idx >= BEG && idx < END) D[i][j] = Tile<T>::mma(M[k][i][r], Y[k][j][r], D[i][j]);
+}
+
 // Load the lower tiles (i >= j) of a rows×cols column-major matrix; upper tiles zeroed.
 template <typename T, int NT, bool FULL = false>
 __device__ __forceinline__ void tiles_load_lower(typename Tile<T>::acc (&D)[NT][NT], const T *__restrict__ src,
@@ -201,8 +223,51 @@ __device__ __forceinline__ void tiles_load_lower(typename Tile<T>::acc (&D)[NT][
 // Needed for the fast form P_ = Q + AᵀPA − GᵀK, whose accuracy relies on P staying
 // symmetric (GᵀK equals the reference's APB·K only for symmetric P).  Goes through an
 // NT·16 × NT·16 column-major LDS image with column stride NT·16 + 2.  Every LDS read is
-// unconditional and the diagonal tiles blend with a bit mask (no exec-mask branches: a
-// predicated read costs ~6 scalar/VALU instructions plus an SGPR-spill readlane).
+// unconditional.  A diagonal tile reads element (max(row, col), min(row, col)) of the image —
+// its own value on and below the diagonal, the mirror above it — so the value read IS the
+// symmetrized one: no select, no lane mask.  Those addresses do not depend on the knot or
+// on the tile (tile (i, i) is a constant offset from tile (0, 0), folded into the ds_read
+// immediate): symmetrize_diag_index() forms them once, one per register r.
+template <typename T, int NT>
+__device__ __forceinline__ void symmetrize_diag_index(int (&idx)[4], int lane)
+{
+    constexpr int S = NT * 16 + 2;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int row = Tile<T>::row(lane, r), col = tcol(lane);
+        idx[r] = max(row, col) + min(row, col) * S;
+    }
+}
+
+template <typename T, int NT>
+__device__ __forceinline__ void tiles_symmetrize_lower(typename Tile<T>::acc (&D)[NT][NT], T *lds,
+                                                       const int (&didx)[4], int lane)
+{
+    constexpr int S = NT * 16 + 2;
+#pragma unroll
+    for (int i = 0; i < NT; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                lds[(i * 16 + Tile<T>::row(lane, r)) + (j * 16 + tcol(lane)) * S] = D[i][j][r];
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < NT; ++i)
+#pragma unroll
+        for (int j = i; j < NT; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = i * 16 + Tile<T>::row(lane, r), col = j * 16 + tcol(lane);
+                if (j > i) D[i][j][r] = lds[col + row * S];      // strictly upper tile: all mirrored
+                else D[i][j][r] = lds[didx[r] + i * 16 * (S + 1)];
+            }
+    __syncthreads();
+}
+
+// The same without precomputed indices: diagonal tiles read the mirror and blend it in above
+// the diagonal with a bit mask (16 v_cndmask + lane masks per knot at NT = 2 — what the index
+// form above removes; kept for callers outside a knot loop and the ISA negative control).
 __device__ __forceinline__ double blend_upper(double keep, double mirror, bool take)
 {
     const long long m = -(long long)take;                       // all-ones when take
@@ -213,7 +278,6 @@ __device__ __forceinline__ float blend_upper(float keep, float mirror, bool take
     const int m = -(int)take;
     return __int_as_float((__float_as_int(mirror) & m) | (__float_as_int(keep) & ~m));
 }
-
 template <typename T, int NT>
 __device__ __forceinline__ void tiles_symmetrize_lower(typename Tile<T>::acc (&D)[NT][NT], T *lds,
                                                        int lane)
@@ -274,14 +338,27 @@ __device__ __forceinline__ float wave_max(float v)
 // branch on it is uniform): integer max on the float bit pattern (order-preserving for
 // x ≥ 0) through DPP row shifts and row broadcasts (gfx9 DPP), then v_readlane of lane 63.
 // 6 VALU + 1 readlane, no LDS (the xor-butterfly above costs 12 ds_bpermute for a double).
+// Each step is ONE v_max_i32 with the DPP modifier on src0 (written as update_dpp + max the
+// compiler emits v_mov, s_nop 1, v_mov_dpp, v_max per step).  A lane whose DPP source is
+// out of range (bound_ctrl off) or masked off by row_mask keeps its destination — which is
+// v itself, what max(v, update_dpp(old = v, …)) gives there.  VALU only, no memory operand.
+// The two wait states a DPP read needs after the VALU write of the same VGPR (gfx9 data
+// hazard; the compiler does not look inside an asm block) are the s_nop 1 before every step.
 __device__ __forceinline__ int wave_max_uniform_i(int v)
 {
-    v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x111, 0xf, 0xf, false));   // row_shr:1
-    v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x112, 0xf, 0xf, false));   // row_shr:2
-    v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x114, 0xf, 0xf, false));   // row_shr:4
-    v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x118, 0xf, 0xf, false));   // row_shr:8
-    v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x142, 0xa, 0xf, false));   // row_bcast:15
-    v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x143, 0xc, 0xf, false));   // row_bcast:31
+    asm volatile("s_nop 1\n\t"
+                 "v_max_i32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+                 "s_nop 1\n\t"
+                 "v_max_i32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
+                 "s_nop 1\n\t"
+                 "v_max_i32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
+                 "s_nop 1\n\t"
+                 "v_max_i32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
+                 "s_nop 1\n\t"
+                 "v_max_i32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
+                 "s_nop 1\n\t"
+                 "v_max_i32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf"
+                 : "+v"(v));
     return __builtin_amdgcn_readlane(v, 63);
 }
 __device__ __forceinline__ float wave_max_uniform(float x)

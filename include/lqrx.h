@@ -45,7 +45,10 @@ extern "C" {
                                    KKT blocks past 64 rows (up to 512, w up to 1024);
                                    KKT layout 1 for every structure (staged);
                                    lqrx_dp_compute_ctg[_host] (per-knot surface);
-                                5: lqrx_*_host_devices (one call sharded over GPUs) */
+                                5: lqrx_*_host_devices (one call sharded over GPUs);
+                                   lqrx_dp_solve_affine[_host] are additive to ABI 5 (no
+                                   existing signature or struct changed, the number stays 5):
+                                   detect them by symbol (dlsym) */
 
 #define LQRX_F64 0
 #define LQRX_F32 1
@@ -158,6 +161,42 @@ int lqrx_dp_solve_linear_host(const lqrx_dp_desc *desc, const void *A, const voi
                               const void *Q, const void *R, const void *Qf, const void *x0,
                               const lqrx_dp_linear *lin, void *K, void *P, void *X, void *U,
                               int32_t *info);
+
+/* ------------------------------------------------------------------------------------
+ * DP path with affine dynamics  x_{k+1} = A_k x_k + B_k u_k + c_k  — what a linearisation
+ * about a non-equilibrium trajectory yields (reference tracking, the defect of a
+ * multiple-shooting / SQP iterate, a gravity or disturbance feed-through); together with
+ * the linear cost terms above this is the whole LQ subproblem of an iLQR / SQP / MPC
+ * caller.  With V_{k+1}(x) = ½xᵀP x + pᵀx, E = R_k + BᵀPB, G = BᵀPA:
+ *   p̃   = p_{k+1} + P_{k+1} c_k
+ *   K_k = E⁻¹G                     (K, P and info do not depend on c, q, r)
+ *   d_k = E⁻¹(r_k + Bᵀp̃)          p_k = q_k + Aᵀp̃ − Gᵀd_k          P_k = Q_k + AᵀPA − GᵀK_k
+ *   rollout: u_k = −K_k x_k − d_k,  x_{k+1} = A_k x_k + B_k u_k + c_k
+ * i.e. lqrx_dp_solve_linear's recursion with p̃ in place of p.  (The constant of the value
+ * function is not formed.)  Same descriptor, inputs and outputs as lqrx_dp_solve_linear plus
+ *   c   n·batch, or n·(N−1)·batch when knot_stride_AB = 1 (knot k at k−1: c follows A and B
+ *       as q and r follow Q and R); desc.layout applies to it as to every array.
+ * lin is required with all five pointers non-NULL (a caller without cost terms passes zero
+ * q, r, qf); d and p are outputs as above.  All-zero c gives the lqrx_dp_solve_linear results.
+ * Error codes follow the argument position: desc −1, A −2, B −3, c −4, Q −5, R −6, Qf −7,
+ * x0 −8, lin or one of its members −9, K −10, P −11, X −12, U −13; batch = 0 returns 0.
+ * Every (n, m, dtype, layout, knot stride, p_mode) lqrx_dp_solve_linear accepts is accepted.
+ * Kernel routing differs from lqrx_dp_solve_linear in two places: n ≤ 4 always takes the
+ * lane-per-trajectory kernel (never the four-lane kernel of small time-invariant batches),
+ * and fp64 n = 64, m ∈ {16, 32} takes the one-wave register-tiled kernel (the LQRX_DP_WG4=0
+ * path), not the four-wave kernel.  There is no _host_devices twin and no affine
+ * lqrx_dp_compute_ctg.  Additive to ABI 5: detect by symbol.
+ * ------------------------------------------------------------------------------------ */
+int lqrx_dp_solve_affine(const lqrx_dp_desc *desc, const void *A, const void *B, const void *c,
+                         const void *Q, const void *R, const void *Qf, const void *x0,
+                         const lqrx_dp_linear *lin, void *K, void *P, void *X, void *U,
+                         int32_t *info, void *stream);
+
+/* host pointers in lin and everywhere else: H2D, solve, D2H, synchronous */
+int lqrx_dp_solve_affine_host(const lqrx_dp_desc *desc, const void *A, const void *B,
+                              const void *c, const void *Q, const void *R, const void *Qf,
+                              const void *x0, const lqrx_dp_linear *lin, void *K, void *P,
+                              void *X, void *U, int32_t *info);
 
 /* ------------------------------------------------------------------------------------
  * KKT path: one inner solve of CholeskySolver._solve!(solver)

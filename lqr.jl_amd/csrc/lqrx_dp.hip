@@ -38,6 +38,10 @@
 #ifndef LQRX_DP_TVWAVES
 #define LQRX_DP_TVWAVES 0   // 0: per tile grid (launch_dp_tv); 1 or 2 forces waves/SIMD (A/B builds)
 #endif
+#ifndef LQRX_DP_AFFWAVES
+#define LQRX_DP_AFFWAVES 0  // 0: the linear-terms launch bound (launch_dp_tv); 1 or 2 forces waves/SIMD of the
+                            // time-invariant VAR_AFF launch (A/B builds)
+#endif
 #ifndef LQRX_DP_TVEXTRA
 #define LQRX_DP_TVEXTRA 0   // extra VAR bits for the time-varying launch (ablations, tools only)
 #endif
@@ -362,7 +366,7 @@ template <typename T, int NT, int MT> struct DpCfg {
 // DEPTH knots ahead, 64 lanes × KPL coalesced elements per knot, staged through LDS.
 // Dot products are split over the wave: u_i by SU = 64/MP lanes (i = lane % MP), x'_i by
 // SX = 64/NP lanes (i = lane % NP), partial sums combined with xor-shuffles.
-template <typename T, int NT, int MT, int DEPTH, bool TV = false, bool LIN = false>
+template <typename T, int NT, int MT, int DEPTH, bool TV = false, bool LIN = false, bool AFF = false>
 __device__ __forceinline__ void dp_rollout(const DpArgs &a, int64_t b, T *lds, int lane)
 {
     using C = DpCfg<T, NT, MT>;
@@ -427,6 +431,12 @@ __device__ __forceinline__ void dp_rollout(const DpArgs &a, int64_t b, T *lds, i
     auto issue_d = [&](int kk, T &dst) {
         if constexpr (LIN) dst = (kk <= N - 1 && lane < m) ? Dg[(size_t)(kk - 1) * m + lane] : (T)0;
     };
+    // affine offset c_k (AFF): row `lane` of it, per knot with A_k, B_k (read at the top of the
+    // knot, used at its end) or once
+    const size_t sc = (AFF && TV && a.tv_AB) ? (size_t)n : 0;
+    const T *Cg = AFF ? (const T *)a.c + (size_t)b * n * (sc ? (size_t)(N - 1) : 1) : nullptr;
+    T cx = (T)0;
+    if constexpr (AFF && !TV) cx = lane < n ? Cg[lane] : (T)0;
 #pragma unroll
     for (int d = 0; d < DEPTH; ++d) {
         issue(1 + d, ring[d]);
@@ -453,6 +463,7 @@ __device__ __forceinline__ void dp_rollout(const DpArgs &a, int64_t b, T *lds, i
                 if constexpr (TV) {
                     if (k + AD <= N - 1) load_rows(k + AD, arow_n[AD - 1], brow_n[AD - 1]);   // AD knots ahead
                 }
+                if constexpr (AFF && TV) cx = lane < n ? Cg[(size_t)(k - 1) * sc + lane] : (T)0;
                 __syncthreads();
                 // u_i = −Σ_j K[i][j] x_j   (dynamic_programming.jl:68)
                 T s0 = 0, s1 = 0;
@@ -483,6 +494,7 @@ __device__ __forceinline__ void dp_rollout(const DpArgs &a, int64_t b, T *lds, i
                 T xn = t0 + t1;
 #pragma unroll
                 for (int o = NP; o < 64; o <<= 1) xn += __shfl_xor(xn, o);
+                if constexpr (AFF) xn += cx;                             // + c_k
                 __syncthreads();
                 if (lane < n) {
                     xs[lane] = xn;
@@ -556,7 +568,7 @@ __device__ __forceinline__ void vm_wait_regs(T (&r)[C], T &d)
 // the row; x_{k+1} = A x + B u with A, B rows in registers (lane l: row l mod NP, a
 // contiguous column run); x and u pass between lanes through LDS, read as contiguous runs;
 // the wave is its own workgroup, so wave-level ordering (wsync) replaces barriers.
-template <typename T, int NT, int MT, int DEPTH, bool LIN>
+template <typename T, int NT, int MT, int DEPTH, bool LIN, bool AFF = false>
 __device__ __forceinline__ void dp_rollout_full(const DpArgs &a, int64_t b, T *lds, int lane)
 {
     constexpr int NP = 16 * NT, MP = 16 * MT;
@@ -584,6 +596,8 @@ __device__ __forceinline__ void dp_rollout_full(const DpArgs &a, int64_t b, T *l
         xs[lane] = v;
         Xg[lane] = v;
     }
+    T cx = (T)0;                                       // affine offset c (AFF): row ix
+    if constexpr (AFF) cx = ((const T *)a.c)[(size_t)b * NP + ix];
     // K_kk (knot kk = 1 … N−1; past the end: the last knot again, never used).  The loads are
     // inline asm, invisible to the compiler's wait-count pass, which would otherwise wait at
     // the loop header for the loads issued one knot earlier instead of DEPTH knots earlier;
@@ -655,6 +669,7 @@ __device__ __forceinline__ void dp_rollout_full(const DpArgs &a, int64_t b, T *l
         T xn = t0 + t1;
 #pragma unroll
         for (int o = NP; o < 64; o <<= 1) xn += xor_shfl(xn, (lane ^ o) << 2);
+        if constexpr (AFF) xn += cx;                   // + c
         wsync_w();
         if (hx == 0) {
             xs[ix] = xn;
@@ -702,8 +717,15 @@ __device__ __forceinline__ void dp_rollout_full(const DpArgs &a, int64_t b, T *l
 //                with VAR_TV: K = XᵀG's companion d = Xᵀ(r + Bᵀp) and p ← q + Aᵀp − Gᵀd
 //                (Gᵀ = APB for symmetric P) on the VALU — the vectors are exchanged through
 //                a small LDS image (lin_* helpers below).
+//   VAR_AFF    : affine dynamics x⁺ = Ax + Bu + c (lqrx_dp_solve_affine), only with VAR_LIN, with
+//                or without VAR_TV: the recursion is VAR_LIN's with p̃ = p + P c_k in place of p in
+//                its two uses (w = r + Bᵀp̃, Aᵀp̃).  P c_k = Pᵀc_k (P is exactly symmetric after
+//                tiles_symmetrize_lower) is one more lin_tn-style sum over the P tiles, added
+//                into the p image before lin_first() reads it (aff_ptilde() in the kernel: at the
+//                head of lin_first() time-varying, behind the PA product time-invariant); the
+//                rollout adds c_k to x_{k+1}.
 enum : int { VAR_NOSOLVE = 2, VAR_NOROLL = 4, VAR_NOKSTORE = 8, VAR_SWEEPONLY = 16, VAR_TV = 32,
-             VAR_LIN = 64 };
+             VAR_LIN = 64, VAR_AFF = 128 };
 
 // Vector products with register tiles (VAR_LIN).  A vector v is read from its LDS image in
 // "row layout" (lane l, slot [i][r] = v[16i + Tile::row(l, r)], the rows a C-layout tile's
@@ -741,13 +763,16 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
     using C = DpCfg<T, NT, MT>;
     using acc = typename Tile<T>::acc;
     constexpr int MP = C::MP, CS = C::CS;
-    constexpr bool TV = (VAR & VAR_TV) != 0, LIN = (VAR & VAR_LIN) != 0;
+    constexpr bool TV = (VAR & VAR_TV) != 0, LIN = (VAR & VAR_LIN) != 0, AFF = (VAR & VAR_AFF) != 0;
+    static_assert(!AFF || LIN, "VAR_AFF extends VAR_LIN");
     // Q + AᵀPA in the shadow of the Newton–Schulz chain (PnShadow): time-invariant A only
     constexpr bool SHADOW = !TV && (VAR & (VAR_NOSOLVE | VAR_SWEEPONLY)) == 0;
     constexpr int NP = C::NP;
     __shared__ T lds[C::LDS_ELEMS];
-    // p (NP), then w / d (MP); time-invariant q (NP), r (MP) images after them
-    __shared__ T vimg[LIN ? (TV ? NP + MP : 2 * (NP + MP)) : 1];
+    // p (NP), then w / d (MP); time-invariant q (NP), r (MP) images after them; VAR_AFF: one more
+    // NP slot, the time-invariant c image
+    constexpr int CIMG = TV ? NP + MP : 2 * (NP + MP);
+    __shared__ T vimg[LIN ? CIMG + (AFF ? NP : 0) : 1];
     // Q (time-invariant, read every knot as the P_ accumulator start) lives in LDS for the
     // horizon: an LDS read per element instead of an L2 round trip per knot
     __shared__ T qimg[TV ? 1 : C::QIMG];
@@ -794,6 +819,9 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
     const T *rg = LIN ? (const T *)a.r + (size_t)b * m * kQR : nullptr;
     T *dg = LIN ? (T *)a.d + (size_t)b * (size_t)(N - 1) * m : nullptr;
     T *pallv = (LIN && a.p_all) ? (T *)a.p + (size_t)b * (size_t)N * n : nullptr;
+    // affine offset c_k: knot stride with A, B
+    const size_t sc = (AFF && kAB > 1) ? (size_t)n : 0;
+    const T *cg = AFF ? (const T *)a.c + (size_t)b * n * kAB : nullptr;
     if constexpr (LIN) {
         const T *qf = (const T *)a.qf + (size_t)b * n;
         for (int i = lane; i < NP; i += 64) {
@@ -801,6 +829,7 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
             vimg[i] = v;
             if (pallv && i < n) pallv[(size_t)(N - 1) * n + i] = v;
             if constexpr (!TV) vimg[NP + MP + i] = i < n ? qg[i] : (T)0;
+            if constexpr (AFF && !TV) vimg[CIMG + i] = i < n ? cg[i] : (T)0;
         }
         if constexpr (!TV) {
             for (int i = lane; i < MP; i += 64) vimg[2 * NP + MP + i] = i < m ? rg[i] : (T)0;
@@ -851,10 +880,57 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
                 rv[j] = i < m ? rg[(size_t)(k - 1) * sr + i] : (T)0;
             }
         }
+        // c_k in row layout (lin_rows' slots), time-varying: from global beside q_k, r_k
+        T crow[(AFF && TV) ? NT : 1][4];
+        if constexpr (AFF && TV) {
+#pragma unroll
+            for (int i = 0; i < NT; ++i)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int e = 16 * i + Tile<T>::row(lane, r);
+                    crow[i][r] = (FULL || e < n) ? cg[(size_t)(k - 1) * sc + e] : (T)0;
+                }
+        }
+        // VAR_AFF: p̃ = p + P c_k, in place in the p image (the image is rewritten whole at the end
+        // of the knot).  Every lane's reads of p from the knot before are behind that knot's closing
+        // barrier, and slot 16j + lane was last written by this lane, so one barrier — after the
+        // add, before lin_first() reads the image in row layout — is all it needs.  P c = Pᵀc: one
+        // row tile of c at a time (lin_tn's sum with four c values live).
+        // Time-varying: at the head of lin_first(), which follows the knot's products directly.
+        // Time-invariant: here, behind P's last MFMA use, not in lin_first() after the solve —
+        // P is dead from here on in the VAR_LIN variant, and holding its 8·NT² registers across
+        // the solve for one mat-vec spilled 36 VGPRs on the fp64 2×1 grid at 2 waves/SIMD.
+        auto aff_ptilde = [&]() {
+            if constexpr (AFF) {
+                T pc[NT];
+#pragma unroll
+                for (int j = 0; j < NT; ++j) pc[j] = (T)0;
+#pragma unroll
+                for (int i = 0; i < NT; ++i) {
+                    T cr[4];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        if constexpr (TV) cr[r] = crow[i][r];
+                        else cr[r] = vimg[CIMG + 16 * i + Tile<T>::row(lane, r)];
+                    }
+#pragma unroll
+                    for (int j = 0; j < NT; ++j)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) pc[j] = fma(P[i][j][r], cr[r], pc[j]);
+                }
+#pragma unroll
+                for (int j = 0; j < NT; ++j) {
+                    const T s = lin_rowsum(pc[j]);
+                    if (lane < 16) vimg[16 * j + lane] += s;
+                }
+                __syncthreads();                       // p̃ complete before the row-layout read
+            }
+        };
         tiles_zero<T, NT, MT>(PB);
         mma_tn<T, NT, NT, MT>(PB, P, Bt);                          // :38 PB = P B
         tiles_zero<T, NT, NT>(PA);
         mma_tn<T, NT, NT, NT>(PA, P, At);                          // :40 PA = P A
+        if constexpr (AFF && !TV) aff_ptilde();
         if constexpr (TV) {
             tiles_load_lower<T, NT, FULL>(Pn, Qb + (size_t)(k - 1) * sQ, n, n, lane);
 #if LQRX_DP_TVWAIT
@@ -880,6 +956,7 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
         T w[LIN ? MT : 1], ap[LIN ? NT : 1];
         auto lin_first = [&]() {
             if constexpr (LIN) {
+                if constexpr (AFF && TV) aff_ptilde();
                 T prow[NT][4];
                 lin_rows<T, NT>(prow, vimg, lane);
 #pragma unroll
@@ -1035,10 +1112,10 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
         __syncthreads();
 #if LQRX_DP_ROLL_FULL
         if constexpr (FULL && !TV && (64 % (16 * NT)) == 0 && (64 % (16 * MT)) == 0)
-            dp_rollout_full<T, NT, MT, LQRX_DP_KD, LIN>(a, b, lds, lane);
+            dp_rollout_full<T, NT, MT, LQRX_DP_KD, LIN, AFF>(a, b, lds, lane);
         else
 #endif
-            dp_rollout<T, NT, MT, TV ? LQRX_DP_TVKD : LQRX_DP_KD, TV, LIN>(a, b, lds, lane);
+            dp_rollout<T, NT, MT, TV ? LQRX_DP_TVKD : LQRX_DP_KD, TV, LIN, AFF>(a, b, lds, lane);
     }
 }
 
@@ -1723,6 +1800,9 @@ static hipError_t launch_dp_tv(const DpArgs &a, hipStream_t s)
     // 1×1 (double) and up to 2×1 (float) grids; time-invariant LIN keeps the plain kernel's
     // occupancy (its vector work sits after the solve, where fewer tiles are live)
     constexpr int LW = (NT * MT <= (sizeof(T) == 4 ? 2 : 1)) ? 2 : 1;
+    // affine offset (needs lin): the launch bounds of the linear-terms variants
+    if (a.aff && (a.tv_AB || a.tv_QR)) return launch_dp<T, NT, MT, LW, VAR_TV | VAR_LIN | VAR_AFF>(a, s);
+    if (a.aff) return launch_dp<T, NT, MT, LQRX_DP_AFFWAVES ? LQRX_DP_AFFWAVES : WAVES, VAR_LIN | VAR_AFF>(a, s);
     if (a.lin && (a.tv_AB || a.tv_QR)) return launch_dp<T, NT, MT, LW, VAR_TV | VAR_LIN>(a, s);
     if (a.lin) return launch_dp<T, NT, MT, WAVES, VAR_LIN>(a, s);
     if (a.tv_AB || a.tv_QR) return launch_dp<T, NT, MT, TVW, VAR_TV | LQRX_DP_TVEXTRA>(a, s);
@@ -1766,7 +1846,8 @@ hipError_t dp_launch(const DpArgs &a_in, hipStream_t s)
         // or without linear terms (LQRX_DP_WG4=0 in the environment: the one-wave kernel, for A/B
         // runs and tests)
         static const bool wg4 = [] { const char *e = std::getenv("LQRX_DP_WG4"); return LQRX_DP_WG4 && !(e && *e == '0'); }();
-        if (wg4 && a.n == 64 && (a.m == 16 || a.m == 32))
+        // (an affine call takes the one-wave kernel below: dp_wg4_kernel has no c_k)
+        if (wg4 && !a.aff && a.n == 64 && (a.m == 16 || a.m == 32))
             return a.m == 16 ? launch_wg4<1>(a, s) : launch_wg4<2>(a, s);
         if (nt <= 4 && mt <= 2) return launch_dp_tv<double, 4, 2, 1>(a, s);   // n ≤ 64: 1 wave/SIMD
     } else {

@@ -11,7 +11,9 @@
 // the 4 waves take output tiles round-robin and stream strided operand tiles from L2), the factor
 // and the triangular solves blocked by 16 with their updates on MFMA too (lqrx_wg.h), the rollout
 // on the VALU.
-// Time-varying knot strides, all-P output, linear cost terms (d, p) as in the other kernels.
+// Time-varying knot strides, all-P output, linear cost terms (d, p) as in the other kernels; the
+// affine offset c_k of lqrx_dp_solve_affine (a.aff, with a.lin): p ← p + P c_k at the head of the
+// knot, before w = r + Bᵀp, and x_{k+1} += c_k in the rollout.
 #include "lqrx_internal.h"
 #include "lqrx_tile.h"
 #include "lqrx_wg.h"
@@ -41,6 +43,9 @@ __global__ __launch_bounds__(BT) void dp_big_kernel(const DpArgs a, T *__restric
     const T *Q0 = (const T *)a.Q + b * nn * kQR, *R0 = (const T *)a.R + b * mm * kQR;
     const bool lin = a.lin != 0;
     const size_t sq = a.tv_QR ? (size_t)n : 0, sr = a.tv_QR ? (size_t)m : 0;
+    const bool aff = lin && a.aff != 0;
+    const size_t sc = a.tv_AB ? (size_t)n : 0;
+    const T *c0 = aff ? (const T *)a.c + b * n * kAB : nullptr;
 
     T *w0 = ws + (size_t)blockIdx.x * ws_elems;
     T *P = w0, *Pn = P + nn, *PA = Pn + nn, *PB = PA + nn, *APB = PB + nm, *E = APB + nm;
@@ -76,6 +81,15 @@ __global__ __launch_bounds__(BT) void dp_big_kernel(const DpArgs a, T *__restric
         const T *Q = Q0 + (size_t)(k - 1) * sQ, *R = R0 + (size_t)(k - 1) * sR;
         T *K = Kb + (size_t)(k - 1) * nm;
         const Mat<T> Pt{P, (size_t)n, 1}, Am{A, 1, (size_t)n}, Bm{B, 1, (size_t)n}, none{nullptr, 0, 0};
+        if (aff) {                                              // p̃ = p + P c_k (p is replaced by p_ below)
+            const T *c = c0 + (size_t)(k - 1) * sc;
+            for (int i = tid; i < n; i += BT) {
+                T s = 0;
+                for (int j = 0; j < n; ++j) s += P[i + (size_t)j * n] * c[j];
+                pv[i] += s;
+            }
+            __syncthreads();
+        }
         // :38 PB = P*B  (= (Pᵀ)ᵀ·B) ; :40 PA = P*A
         wg::wg_mm<T, 1, 1>(PB, n, n, m, nullptr, Pt, Bm, n, none, none, 0, tid);
         wg::wg_mm<T, 1, 1>(PA, n, n, n, nullptr, Pt, Am, n, none, none, 0, tid);
@@ -165,7 +179,7 @@ __global__ __launch_bounds__(BT) void dp_big_kernel(const DpArgs a, T *__restric
             T s = 0, t = 0;
             for (int j = 0; j < n; ++j) s += A[i + (size_t)j * n] * x[j];
             for (int j = 0; j < m; ++j) t += B[i + (size_t)j * n] * u[j];
-            xn[i] = s + t;
+            xn[i] = aff ? s + t + c0[(size_t)(k - 1) * sc + i] : s + t;
         }
         __syncthreads();
     }

@@ -52,7 +52,10 @@ __device__ __forceinline__ void lane_load(T (&D)[RP][CP], const T *__restrict__ 
 //   d = E⁻¹(r + Bᵀp)  (the same potrf factor, one more potrs column),
 //   p ← q + Aᵀp − APB·d  (APB = AᵀPB = Gᵀ for symmetric P),
 // and the rollout applies u = −(K x + d).  Reference op order: oracle_dp_solve_one_lin.
-template <typename T, int NP, int MP, bool TV, bool SOA, bool LIN = false>
+// AFF (affine dynamics x⁺ = Ax + Bu + c, lqrx_dp_solve_affine; needs LIN; c follows A, B: per
+// knot with TV and tv_AB): p̃ = p + P c_k replaces p in both uses above (formed in registers
+// from the lower triangle of P_{k+1}), and the rollout adds c_k to x_{k+1}.
+template <typename T, int NP, int MP, bool TV, bool SOA, bool LIN = false, bool AFF = false>
 __global__ __launch_bounds__(64) void dp_lane_kernel(const DpArgs a)
 {
     const int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x;
@@ -103,6 +106,15 @@ __global__ __launch_bounds__(64) void dp_lane_kernel(const DpArgs a)
     T *db = LIN ? (T *)a.d + tb((int64_t)(N - 1) * m) : nullptr;
     T *pall = (LIN && a.p_all) ? (T *)a.p + tb((int64_t)N * n) : nullptr;
     T pv[LN], qv[LN], rv[LM], qn[LN], rn[LM];
+    static_assert(!AFF || LIN, "AFF extends LIN");
+    constexpr int CN = AFF ? NP : 1;
+    const int64_t sc = a.tv_AB ? n : 0;
+    const T *cb = AFF ? (const T *)a.c + tb(n * kAB) : nullptr;
+    T cv[CN], cn[CN];
+    if constexpr (AFF && !TV) {   // time-invariant c: loaded once (the rollout reads it too)
+#pragma unroll
+        for (int i = 0; i < NP; ++i) cv[i] = i < n ? cb[i * es] : (T)0;
+    }
     if constexpr (LIN) {
         const T *qf = (const T *)a.qf + tb(n);
 #pragma unroll
@@ -129,6 +141,10 @@ __global__ __launch_bounds__(64) void dp_lane_kernel(const DpArgs a)
             for (int i = 0; i < NP; ++i) qn[i] = i < n ? qb[((int64_t)(k - 1) * sq + i) * es] : (T)0;
 #pragma unroll
             for (int i = 0; i < MP; ++i) rn[i] = i < m ? rb[((int64_t)(k - 1) * sr + i) * es] : (T)0;
+        }
+        if constexpr (AFF) {
+#pragma unroll
+            for (int i = 0; i < NP; ++i) cn[i] = i < n ? cb[((int64_t)(k - 1) * sc + i) * es] : (T)0;
         }
         if constexpr (tvAB) {
             lane_load<T, NP, NP>(An, Ab + (int64_t)(k - 1) * sA * es, n, n, (T)0, es);
@@ -167,9 +183,22 @@ __global__ __launch_bounds__(64) void dp_lane_kernel(const DpArgs a)
 #pragma unroll
             for (int i = 0; i < MP; ++i) rv[i] = rn[i];
         }
+        if constexpr (AFF && TV) {
+#pragma unroll
+            for (int i = 0; i < NP; ++i) cv[i] = cn[i];
+        }
         if constexpr (TV) fetch_tv(k - 1);
         // P is symmetric: only P[i][j], i ≥ j, is maintained
 #define PS(i, j) ((i) >= (j) ? P[i][j] : P[j][i])
+        if constexpr (AFF) {   // p̃ = p + P c_k (p is rewritten whole below)
+#pragma unroll
+            for (int i = 0; i < NP; ++i) {
+                T s = pv[i];
+#pragma unroll
+                for (int l = 0; l < NP; ++l) s = fma(PS(i, l), cv[l], s);
+                pv[i] = s;
+            }
+        }
         T PB[NP][MP], PA[NP][NP];
 #pragma unroll
         for (int i = 0; i < NP; ++i) {
@@ -331,7 +360,7 @@ __global__ __launch_bounds__(64) void dp_lane_kernel(const DpArgs a)
     // register ring (unrolled by RD so every ring index is static).
     constexpr int RD = TV ? 4 : ((MP * NP <= 8) ? 8 : 4);
     struct Knot {
-        T K[MP][NP], A[TV ? NP : 1][TV ? NP : 1], B[TV ? NP : 1][TV ? MP : 1], d[LM];
+        T K[MP][NP], A[TV ? NP : 1][TV ? NP : 1], B[TV ? NP : 1][TV ? MP : 1], d[LM], c[AFF && TV ? NP : 1];
     };
     Knot ring[RD];
     auto fetch = [&](int k, Knot &d) {
@@ -344,6 +373,10 @@ __global__ __launch_bounds__(64) void dp_lane_kernel(const DpArgs a)
         if constexpr (LIN) {
 #pragma unroll
             for (int i = 0; i < MP; ++i) d.d[i] = i < m ? db[((int64_t)(k - 1) * m + i) * es] : (T)0;
+        }
+        if constexpr (AFF && TV) {
+#pragma unroll
+            for (int i = 0; i < NP; ++i) d.c[i] = i < n ? cb[((int64_t)(k - 1) * sc + i) * es] : (T)0;
         }
         if constexpr (tvAB) {
             lane_load<T, NP, NP>(d.A, Ab + (int64_t)(k - 1) * sA * es, n, n, (T)0, es);
@@ -373,6 +406,10 @@ __global__ __launch_bounds__(64) void dp_lane_kernel(const DpArgs a)
                     for (int c = 0; c < MP; ++c) B[i][c] = ring[d].B[i][c];
                 }
             }
+            if constexpr (AFF && TV) {
+#pragma unroll
+                for (int i = 0; i < NP; ++i) cv[i] = ring[d].c[i];
+            }
             fetch(k + RD, ring[d]);
             T u[MP];
 #pragma unroll
@@ -392,6 +429,7 @@ __global__ __launch_bounds__(64) void dp_lane_kernel(const DpArgs a)
                 for (int j = 0; j < NP; ++j) s = fma(A[i][j], x[j], s);
 #pragma unroll
                 for (int c = 0; c < MP; ++c) s = fma(B[i][c], u[c], s);
+                if constexpr (AFF) s += cv[i];   // + c_k
                 xn[i] = s;
             }
 #pragma unroll
@@ -1022,7 +1060,11 @@ static hipError_t launch_lane(const DpArgs &a, hipStream_t s)
 {
     dim3 grid((unsigned)((a.batch + 63) / 64)), block(64);
     const bool tv = a.tv_AB || a.tv_QR, soa = a.layout == 1;
-    if (a.lin && tv && soa) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, true, true, true>), grid, block, 0, s, a);
+    if (a.aff && tv && soa) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, true, true, true, true>), grid, block, 0, s, a);
+    else if (a.aff && tv) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, true, false, true, true>), grid, block, 0, s, a);
+    else if (a.aff && soa) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, false, true, true, true>), grid, block, 0, s, a);
+    else if (a.aff) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, false, false, true, true>), grid, block, 0, s, a);
+    else if (a.lin && tv && soa) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, true, true, true>), grid, block, 0, s, a);
     else if (a.lin && tv) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, true, false, true>), grid, block, 0, s, a);
     else if (a.lin && soa) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, false, true, true>), grid, block, 0, s, a);
     else if (a.lin) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, false, false, true>), grid, block, 0, s, a);
@@ -1040,6 +1082,7 @@ bool dp_lane_supported(int n, int m) { return n >= 1 && m >= 1 && n <= 4 && m <=
 static bool use_quad(const DpArgs &a)
 {
     if (a.tv_AB || a.tv_QR || a.n < 3 || a.n > 4) return false;
+    if (a.aff) return false;   // affine dynamics: dp_lane_kernel only (dp_quad_kernel has no c_k)
     const char *e = std::getenv("LQRX_DP_SMALL");
     if (e && e[0] == 'l') return false;
     if (e && e[0] == 'q') return true;

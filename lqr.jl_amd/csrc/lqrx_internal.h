@@ -27,6 +27,11 @@ struct DpArgs {
     // tests only (LQRX_DP_NS_OFF=1, read by dp_launch): no Newton–Schulz step, every knot takes the
     // exact LDLᵀ sweep — exercises the sweep / verdict paths of the MFMA kernels at every knot
     int ns_off;
+    // affine dynamics x⁺ = A x + B u + c (lqrx_dp_solve_affine; needs lin = 1): c per knot with
+    // tv_AB (knot stride n, knot k at k−1, like A and B), n per trajectory otherwise.  (Last, so
+    // that every earlier field keeps its kernel-argument offset.)
+    int aff;
+    const void *c;
 };
 
 hipError_t dp_launch(const DpArgs &a, hipStream_t s);

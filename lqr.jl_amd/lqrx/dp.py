@@ -8,7 +8,8 @@ Reference surface (Julia, /root/reference/src):
   solve!(sol, solver, prob)                                dynamic_programming.jl:54-72
   compute_gain!(K, solver, prob), compute_ctg!(K, solver, prob)      :34-52 (per knot)
 Extension (no upstream counterpart): linear cost terms q, r, qf on
-LQRProblem / LQRBatch → feedforward d and linear cost-to-go p (lqrx_dp_solve_linear).
+LQRProblem / LQRBatch → feedforward d and linear cost-to-go p (lqrx_dp_solve_linear); an
+affine dynamics offset c, x⁺ = A x + B u + c (lqrx_dp_solve_affine), which also returns d, p.
 
 Array conventions here: a single problem uses plain (rows, cols) numpy matrices; batches
 use numpy arrays shaped (batch, rows, cols).  The C ABI wants Julia column-major with the
@@ -73,6 +74,9 @@ class LQRProblem:
     q: np.ndarray | None = None
     r: np.ndarray | None = None
     qf: np.ndarray | None = None
+    # affine dynamics offset (extension): x_{k+1} = A x_k + B u_k + c; c (n,) or, together with a
+    # knot axis on A and B, (N-1, n)
+    c: np.ndarray | None = None
 
     def size(self):
         n, m = self.B.shape[-2:]
@@ -102,7 +106,7 @@ class LQRSolution:
     @classmethod
     def of(cls, prob: LQRProblem, all_P: bool = False):
         n, m, N = prob.size()
-        lin = prob.q is not None
+        lin = prob.q is not None or prob.c is not None
         return cls(np.zeros((N - 1, m, n)), np.zeros((N, n)), np.zeros((N - 1, m)),
                    np.zeros((N, n, n)) if all_P else np.zeros((n, n)),
                    d=np.zeros((N - 1, m)) if lin else None,
@@ -145,6 +149,7 @@ class LQRBatch:
     q: np.ndarray | None = None    # (batch, n) or (batch, N-1, n) — linear terms (extension)
     r: np.ndarray | None = None    # (batch, m) or (batch, N-1, m)
     qf: np.ndarray | None = None   # (batch, n)
+    c: np.ndarray | None = None    # (batch, n) or (batch, N-1, n) — affine offset x⁺ = Ax + Bu + c
 
     @property
     def batch(self):
@@ -167,9 +172,14 @@ class LQRBatch:
             return np.diag(a) if f in ("Q", "Qf", "R") and a.ndim == 1 else a
         st = lambda f: np.stack([field_(p, f) for p in probs])
         lin = probs[0].q is not None
+        aff = probs[0].c is not None
+        if aff:
+            for p in probs:   # a knot axis on c needs one on A and B, and vice versa
+                if (np.ndim(p.c) == 2) != (np.ndim(p.A) == 3):
+                    raise ValueError("c carries a knot axis (N-1, n) exactly when A and B carry one")
         return cls(st("A"), st("B"), st("Q"), st("R"), st("Qf"), st("x0"), probs[0].N,
                    q=st("q") if lin else None, r=st("r") if lin else None,
-                   qf=st("qf") if lin else None)
+                   qf=st("qf") if lin else None, c=st("c") if aff else None)
 
 
 def _ptr(a: np.ndarray):
@@ -189,12 +199,26 @@ def solve_batch(b: LQRBatch, dtype: int = _lib.F64, all_P: bool = False, layout:
     U (batch, N-1, m), info (batch,), and the ABI return code.  layout = 1 hands the
     library batch-fastest (SoA) buffers (the conversion here is host-side bookkeeping; the
     result is the same logical arrays).  devices = [d0, d1, …] shards the batch over those
-    GPUs in one call (lqrx_dp_solve[_linear]_host_devices; repeats allowed)."""
-    lib = _lib.load()
+    GPUs in one call (lqrx_dp_solve[_linear]_host_devices; repeats allowed).  With b.c (affine
+    dynamics) the call is lqrx_dp_solve_affine_host: missing q, r, qf are zeros, d and p are
+    returned; it has no devices= form."""
     n, m, N = b.size()
     bt = b.batch
     tvAB, tvQR = b.time_varying()
     npdt = np.float64 if dtype == _lib.F64 else np.float32
+    aff = b.c is not None
+    if aff:
+        if devices is not None:
+            raise ValueError("devices= is not available with an affine offset c")
+        if (np.ndim(b.c) == 3) != bool(tvAB):
+            raise ValueError("c carries a knot axis (batch, N-1, n) exactly when A and B carry one")
+        kq = N - 1 if tvQR else 1
+        zeros = lambda *s: np.zeros(s, npdt)
+        b = LQRBatch(b.A, b.B, b.Q, b.R, b.Qf, b.x0, b.N, b.extra,
+                     q=b.q if b.q is not None else (zeros(bt, kq, n) if tvQR else zeros(bt, n)),
+                     r=b.r if b.r is not None else (zeros(bt, kq, m) if tvQR else zeros(bt, m)),
+                     qf=b.qf if b.qf is not None else zeros(bt, n), c=b.c)
+    lib = _lib.load()
     ins = [to_abi(np.asarray(x, dtype=npdt)) for x in (b.A, b.B, b.Q, b.R, b.Qf)]
     x0 = np.ascontiguousarray(np.asarray(b.x0, dtype=npdt))
     if layout == 1:
@@ -222,7 +246,12 @@ def solve_batch(b: LQRBatch, dtype: int = _lib.F64, all_P: bool = False, layout:
                            _ptr(pv).value)
         args = (C.byref(d), *[_ptr(a) for a in ins], _ptr(x0), C.byref(ln), _ptr(K), _ptr(P),
                 _ptr(X), _ptr(U), _ptr(info))
-        if devices is None:
+        if aff:   # c follows A and B: argument 4
+            cv = np.ascontiguousarray(np.asarray(b.c, dtype=npdt).reshape(bt * (N - 1 if tvAB else 1) * n))
+            if layout == 1:
+                cv = to_soa(cv, bt)
+            rc = _lib.check(lib.lqrx_dp_solve_affine_host(*args[:3], _ptr(cv), *args[3:]))
+        elif devices is None:
             rc = _lib.check(lib.lqrx_dp_solve_linear_host(*args))
         else:
             dv, dp_, nd = _devices(devices)
@@ -257,7 +286,7 @@ def solve(sol: LQRSolution, solver: DPSolver, prob: LQRProblem) -> LQRSolution:
     sol.U[...] = out["U"][0]
     sol.P[...] = out["P"][0]
     sol.info = int(out["info"][0])
-    if prob.q is not None:
+    if prob.q is not None or prob.c is not None:
         sol.d = out["d"][0]
         sol.p = out["p"][0]
     return sol
@@ -339,7 +368,8 @@ def dp_solve_device(t: dict, N: int, p_mode: int = 0, stream: int | None = None,
     batch fastest, every input and output).
 
     t: dict with torch tensors A, B, Q, R, Qf, x0 on the GPU and ints n, m, batch; with
-    tensors q, r, qf as well it runs lqrx_dp_solve_linear and also returns d and p.
+    tensors q, r, qf as well it runs lqrx_dp_solve_linear and also returns d and p; with a
+    tensor c too (n·batch, or n·(N−1)·batch with tv_AB) it runs lqrx_dp_solve_affine.
     Returns dict of output tensors (K, P, X, U, info[, d, p]).  `stream` is a raw hipStream_t
     (torch.cuda.current_stream().cuda_stream); None = the null stream, synchronous.
     """
@@ -359,15 +389,22 @@ def dp_solve_device(t: dict, N: int, p_mode: int = 0, stream: int | None = None,
     d = _lib.DpDesc(n, m, N, dtype, bt, layout, p_mode, int(t.get("tv_AB", 0)), int(t.get("tv_QR", 0)))
     p = lambda x: C.c_void_p(x.data_ptr())
     st = C.c_void_p(stream) if stream else None
+    if t.get("c") is not None and t.get("q") is None:
+        raise ValueError("dp_solve_device: c needs q, r, qf (zeros for a problem without cost terms)")
     if t.get("q") is not None:
         if "d" not in out:
             out["d"] = torch.empty(bt * (N - 1) * m, dtype=tdt, device=dev)
             out["p"] = torch.empty(bt * n * (N if p_mode else 1), dtype=tdt, device=dev)
         ln = _lib.DpLinear(t["q"].data_ptr(), t["r"].data_ptr(), t["qf"].data_ptr(),
                            out["d"].data_ptr(), out["p"].data_ptr())
-        rc = lib.lqrx_dp_solve_linear(C.byref(d), p(t["A"]), p(t["B"]), p(t["Q"]), p(t["R"]),
-                                      p(t["Qf"]), p(t["x0"]), C.byref(ln), p(out["K"]),
-                                      p(out["P"]), p(out["X"]), p(out["U"]), p(out["info"]), st)
+        if t.get("c") is not None:
+            rc = lib.lqrx_dp_solve_affine(C.byref(d), p(t["A"]), p(t["B"]), p(t["c"]), p(t["Q"]),
+                                          p(t["R"]), p(t["Qf"]), p(t["x0"]), C.byref(ln), p(out["K"]),
+                                          p(out["P"]), p(out["X"]), p(out["U"]), p(out["info"]), st)
+        else:
+            rc = lib.lqrx_dp_solve_linear(C.byref(d), p(t["A"]), p(t["B"]), p(t["Q"]), p(t["R"]),
+                                          p(t["Qf"]), p(t["x0"]), C.byref(ln), p(out["K"]),
+                                          p(out["P"]), p(out["X"]), p(out["U"]), p(out["info"]), st)
     else:
         rc = lib.lqrx_dp_solve(C.byref(d), p(t["A"]), p(t["B"]), p(t["Q"]), p(t["R"]), p(t["Qf"]),
                                p(t["x0"]), p(out["K"]), p(out["P"]), p(out["X"]), p(out["U"]),

@@ -141,35 +141,94 @@ def dp_extended(A, B, Q, R, Qf, N):
     logical (batch, r, c) float64 arrays; returns K (batch, N−1, m, n) and P (batch, N, n, n)
     as longdouble — the near-exact answer that the fp64 oracle and the GPU are both measured
     against when a recursion is ill-conditioned (tests/test_dp_lane_gpu.py)."""
-    ld = np.longdouble
-    assert np.finfo(ld).eps < 1e-18, "needs x87 extended precision"
-    A, B, Q, R, Qf = (np.asarray(x, dtype=ld) for x in (A, B, Q, R, Qf))
-    bt, n, m = B.shape
+    assert np.finfo(np.longdouble).eps < 1e-18, "needs x87 extended precision"
+    out = dp_reference(A, B, Q, R, Qf, N, dtype=np.longdouble)
+    return out["K"], out["P"]
+
+
+def dp_reference(A, B, Q, R, Qf, N, q=None, r=None, qf=None, c=None, x0=None, dtype=np.float64):
+    """The DP recursion of include/lqrx.h in ONE precision `dtype` (np.float32, np.float64 or
+    np.longdouble), batched over trajectories: the backward pass of dynamic_programming.jl:54-64
+    in the reference's op order, with the extensions of lqrx_dp_solve_linear / _affine —
+        p̃ = p + P c,  d = E⁻¹(r + Bᵀp̃),  p ← q + Aᵀp̃ − APB·d
+    — when q, r, qf (and c) are given.  The solve is this function's own potrf 'U' + potrs
+    (loops, no LAPACK call), so every operation runs in `dtype`, whatever it is.
+    Inputs are logical arrays: A (batch, n, n), B (batch, n, m), Q, R, Qf, q (batch, n),
+    r (batch, m), qf (batch, n), c (batch, n), x0 (batch, n); A, B, Q, R, q, r, c may carry a
+    knot axis of length N−1 after the batch axis (knot k at index k−1).  Linear terms need q, r
+    and qf together; c alone runs with zero q, r, qf.
+    Returns a dict: K (batch, N−1, m, n), P (batch, N, n, n), info (batch,: the first knot whose
+    E has a non-positive pivot, 0 if none); with linear terms d (batch, N−1, m) and p
+    (batch, N, n); with x0 the rollout X (batch, N, n), U (batch, N−1, m)."""
+    dt = np.dtype(dtype).type
+    cast = lambda x: None if x is None else np.asarray(x, dtype=dt)
+    A, B, Q, R, Qf, q, r, qf, c, x0 = (cast(x) for x in (A, B, Q, R, Qf, q, r, qf, c, x0))
+    bt, n, m = B.shape[0], B.shape[-2], B.shape[-1]
+    lin = q is not None or c is not None
+    if lin:
+        if (q is None) != (r is None) or (q is None) != (qf is None):
+            raise ValueError("linear cost terms need q, r and qf together")
+        if q is None:
+            q, r, qf = np.zeros((bt, n), dt), np.zeros((bt, m), dt), np.zeros((bt, n), dt)
+    at = lambda M, k, nd: M[:, k - 1] if M.ndim == nd + 1 else M      # knot k of a field
     T = lambda M: np.swapaxes(M, 1, 2)
+    mv = lambda M, v: (M @ v[:, :, None])[:, :, 0]
     P = Qf.copy()
-    Ks = np.zeros((bt, N - 1, m, n), dtype=ld)
-    Ps = np.zeros((bt, N, n, n), dtype=ld)
+    Ks = np.zeros((bt, N - 1, m, n), dtype=dt)
+    Ps = np.zeros((bt, N, n, n), dtype=dt)
     Ps[:, N - 1] = P
+    info = np.zeros(bt, np.int32)
+    if lin:
+        p = qf.copy()
+        ds = np.zeros((bt, N - 1, m), dtype=dt)
+        ps = np.zeros((bt, N, n), dtype=dt)
+        ps[:, N - 1] = p
     for k in range(N - 1, 0, -1):
-        PB = P @ B                                   # :38
-        E = R + T(B) @ PB                            # :39
-        PA = P @ A                                   # :40
-        K = T(B) @ PA                                # :41
+        Ak, Bk, Qk, Rk = at(A, k, 3), at(B, k, 3), at(Q, k, 3), at(R, k, 3)
+        PB = P @ Bk                                  # :38
+        E = Rk + T(Bk) @ PB                          # :39
+        PA = P @ Ak                                  # :40
+        K = T(Bk) @ PA                               # :41
+        if lin:
+            pt = p if c is None else p + mv(P, at(c, k, 2))
+            K = np.concatenate([K, (at(r, k, 2) + mv(T(Bk), pt))[:, :, None]], axis=2)
         U = np.zeros_like(E)                         # :29 potrf 'U'
-        for j in range(m):
-            d = E[:, j, j] - (U[:, :j, j] ** 2).sum(axis=1)
-            U[:, j, j] = np.sqrt(d)
-            for c in range(j + 1, m):
-                U[:, j, c] = (E[:, j, c] - (U[:, :j, j] * U[:, :j, c]).sum(axis=1)) / U[:, j, j]
-        for i in range(m):                           # :30 potrs: Uᵀ Y = K, then U X = Y
-            K[:, i] = (K[:, i] - (U[:, :i, i, None] * K[:, :i]).sum(axis=1)) / U[:, i, i, None]
-        for i in range(m - 1, -1, -1):
-            K[:, i] = (K[:, i] - (U[:, i, i + 1:, None] * K[:, i + 1:]).sum(axis=1)) / U[:, i, i, None]
-        APB = T(A) @ PB                              # :50
-        P = Q + T(A) @ PA - APB @ K                  # :51
+        with np.errstate(invalid="ignore", divide="ignore"):
+            for j in range(m):
+                d = E[:, j, j] - (U[:, :j, j] ** 2).sum(axis=1)
+                info[(info == 0) & ~(d > 0)] = k
+                U[:, j, j] = np.sqrt(d)
+                for cc in range(j + 1, m):
+                    U[:, j, cc] = (E[:, j, cc] - (U[:, :j, j] * U[:, :j, cc]).sum(axis=1)) / U[:, j, j]
+            for i in range(m):                       # :30 potrs: Uᵀ Y = K, then U X = Y
+                K[:, i] = (K[:, i] - (U[:, :i, i, None] * K[:, :i]).sum(axis=1)) / U[:, i, i, None]
+            for i in range(m - 1, -1, -1):
+                K[:, i] = (K[:, i] - (U[:, i, i + 1:, None] * K[:, i + 1:]).sum(axis=1)) / U[:, i, i, None]
+        APB = T(Ak) @ PB                             # :50
+        if lin:
+            K, dk = K[:, :, :n], K[:, :, n]
+            p = at(q, k, 2) + mv(T(Ak), pt) - mv(APB, dk)
+            ds[:, k - 1] = dk
+            ps[:, k - 1] = p
+        P = Qk + T(Ak) @ PA - APB @ K                # :51
         Ks[:, k - 1] = K
         Ps[:, k - 1] = P
-    return Ks, Ps
+    out = dict(K=Ks, P=Ps, info=info)
+    if lin:
+        out.update(d=ds, p=ps)
+    if x0 is not None:
+        X = np.zeros((bt, N, n), dtype=dt)
+        Uo = np.zeros((bt, N - 1, m), dtype=dt)
+        X[:, 0] = x0
+        for k in range(1, N):                        # :66-70
+            Uo[:, k - 1] = -mv(Ks[:, k - 1], X[:, k - 1])
+            if lin:
+                Uo[:, k - 1] -= ds[:, k - 1]
+            X[:, k] = mv(at(A, k, 3), X[:, k - 1]) + mv(at(B, k, 3), Uo[:, k - 1])
+            if c is not None:
+                X[:, k] += at(c, k, 2)
+        out.update(X=X, U=Uo)
+    return out
 
 
 def dp_dense_kkt(A, B, Q, R, Qf, x0, N, q=None, r=None, qf=None, with_lam=False):

@@ -4,6 +4,10 @@
 #include "lqrx_internal.h"
 #define LQRX_STR2(x) #x
 #define LQRX_STR(x) LQRX_STR2(x)
+// set by the Makefile: SHA-256 of the library sources (lqrx_build_info; results unaffected)
+#ifndef LQRX_SRC_HASH
+#define LQRX_SRC_HASH "unknown"
+#endif
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -187,9 +191,6 @@ hipError_t dp_launch_soa_staged(const lqrx::DpArgs &a, hipStream_t s)
 extern "C" {
 
 int lqrx_abi_version(void) { return LQRX_ABI_VERSION; }
-#ifndef LQRX_SRC_HASH
-#define LQRX_SRC_HASH "unknown"
-#endif
 const char *lqrx_build_info(void)
 {
     return "src_sha256=" LQRX_SRC_HASH " abi=" LQRX_STR(LQRX_ABI_VERSION) " arch=gfx950 built=" __DATE__ " " __TIME__;

@@ -26,48 +26,23 @@
 #include "lqrx_tile.h"
 #include "lqrx_internal.h"
 
-#ifndef LQRX_DP_WAVES
-#define LQRX_DP_WAVES 2
-#endif
-#ifndef LQRX_DP_BCAST
-#define LQRX_DP_BCAST 0
-#endif
-#ifndef LQRX_DP_VAR
-#define LQRX_DP_VAR 0
-#endif
-#ifndef LQRX_DP_TVWAVES
-#define LQRX_DP_TVWAVES 0   // 0: per tile grid (launch_dp_tv); 1 or 2 forces waves/SIMD (A/B builds)
-#endif
-#ifndef LQRX_DP_AFFWAVES
-#define LQRX_DP_AFFWAVES 0  // 0: the linear-terms launch bound (launch_dp_tv); 1 or 2 forces waves/SIMD of the
-                            // time-invariant VAR_AFF launch (A/B builds)
-#endif
+// ---- build switches of this file (diagnostics for tools/tv_ablate.sh; the library build sets
+// none of them).  Runtime switches (getenv, read in dp_launch): LQRX_DP_WG4, LQRX_DP_NS_OFF,
+// LQRX_DP_BIG. ----
 #ifndef LQRX_DP_TVEXTRA
-#define LQRX_DP_TVEXTRA 0   // extra VAR bits for the time-varying launch (ablations, tools only)
+#define LQRX_DP_TVEXTRA 0   // extra VAR bits for the time-varying launch (VAR_NOROLL …): timing only,
+                            // the results of such a build are incomplete or wrong
 #endif
 #ifndef LQRX_DP_TVABL
-#define LQRX_DP_TVABL 0     // ablation (tools only): re-read knot-1 inputs, see the kernel
-#endif
-#ifndef LQRX_DP_TVAD
-#define LQRX_DP_TVAD 1      // time-varying rollout: knots of A_k/B_k row prefetch (A/B builds)
-#endif
-#ifndef LQRX_DP_KD
-#define LQRX_DP_KD 4        // rollout: knots of K_k prefetch (A/B builds)
-#endif
-#ifndef LQRX_DP_TVKD
-#define LQRX_DP_TVKD 4      // time-varying rollout: knots of K_k prefetch (A/B builds)
-#endif
-#ifndef LQRX_DP_TVWAIT
-#define LQRX_DP_TVWAIT 0
-#endif
-#ifndef LQRX_DP_WG4
-#define LQRX_DP_WG4 1         // fp64 n = 64: the four-wave kernel (A/B builds: 0 = one wave)
-#endif
-#ifndef LQRX_DP_ROLL_FULL
-#define LQRX_DP_ROLL_FULL 1   // exact tile grids: the register-streamed rollout (A/B builds: 0)
+#define LQRX_DP_TVABL 0     // re-read knot-1 inputs (bit 1: Q_k, bit 2: A_k/B_k/R_k): timing only,
+                            // wrong results
 #endif
 
 namespace lqrx {
+
+constexpr int LQRX_DP_TVAD = 1;   // time-varying rollout: knots of A_k/B_k row prefetch
+constexpr int LQRX_DP_KD = 4;     // rollout: knots of K_k prefetch
+constexpr int LQRX_DP_TVKD = 4;   // time-varying rollout: knots of K_k prefetch
 
 // wave-level ordering of LDS traffic between the lanes of a one-wave workgroup (the LDS is in
 // order per wave; this is the compiler fence + wave barrier, no s_barrier)
@@ -99,18 +74,17 @@ __device__ __forceinline__ float xor_shfl(float v, int addr)
 // potrf failure test "pivot ≤ 0" is unchanged).  One column of [E | G | I] per lane
 // (columns lane + 64q).  Step i:  piv = E'[i][i] (v_readlane of lane i), t = x[i]/piv,
 // x[p] −= E'[i][p]·t for p > i, where the unscaled pivot row E'[i][p] reaches every lane
-// as a uniform LDS read (BCAST = 1) or v_readlane (BCAST = 0).  Afterwards
+// by v_readlane.  Afterwards
 //   G columns hold Y = L⁻¹G,  I columns hold W = L⁻¹,  and rinv[i] = 1/piv_i,
 // so  K = E⁻¹G = Wᵀ·(D⁻¹Y)  — finished by the caller as one TN MFMA product.
 // Column images written back to LDS: aug[MP..MP+NP) ← Y, aug[MP+NP..2MP+NP) ← W,
 // rinv (MP values) at aug + (2MP+NP)·CS.  Returns false if a pivot was not > 0.
-template <typename T, int MP, int NP, int CS, int BCAST>
+template <typename T, int MP, int NP, int CS>
 __device__ __forceinline__ bool aug_ldl_forward(T *aug, int lane)
 {
     constexpr int NC = MP + NP + MP;
     constexpr int CPL = (NC + 63) / 64;
-    T *rowbuf = aug + NC * CS;        // 64-wide broadcast row (reused every step)
-    T *rinv = rowbuf + 64;            // 1/pivot per row
+    T *rinv = aug + NC * CS + 64;     // 1/pivot per row (after a 64-wide row that is no longer used)
     T x[CPL][MP];
 #pragma unroll
     for (int q = 0; q < CPL; ++q) {
@@ -126,10 +100,6 @@ __device__ __forceinline__ bool aug_ldl_forward(T *aug, int lane)
     bool ok = true;
 #pragma unroll
     for (int i = 0; i < MP; ++i) {
-        if constexpr (BCAST == 1) {
-            // publish row i of E' (final after step i-1) for the uniform reads below
-            rowbuf[lane] = x[0][i];   // 64-wide row buffer: no exec mask
-        }
         T piv = readlane(x[i / 64][i], i % 64);
         ok = ok && (piv > (T)0);
         T ri = rcp_nr(piv);
@@ -137,16 +107,12 @@ __device__ __forceinline__ bool aug_ldl_forward(T *aug, int lane)
         T t[CPL];
 #pragma unroll
         for (int q = 0; q < CPL; ++q) t[q] = x[q][i] * ri;
-        if constexpr (BCAST == 1) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 #pragma unroll
         for (int p = i + 1; p < MP; ++p) {
-            T e;
-            if constexpr (BCAST == 1) e = rowbuf[p];
-            else e = readlane(x[p / 64][i], p % 64);
+            const T e = readlane(x[p / 64][i], p % 64);
 #pragma unroll
             for (int q = 0; q < CPL; ++q) x[q][p] = fma(-e, t[q], x[q][p]);
         }
-        if constexpr (BCAST == 1) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
@@ -933,9 +899,6 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
         if constexpr (AFF && !TV) aff_ptilde();
         if constexpr (TV) {
             tiles_load_lower<T, NT, FULL>(Pn, Qb + (size_t)(k - 1) * sQ, n, n, lane);
-#if LQRX_DP_TVWAIT
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
         }
         else tiles_lower_from_lds<T, NT>(Pn, qimg, C::QCS, lane);       // P_ ← Q (lower tiles)
 #pragma unroll
@@ -1018,7 +981,7 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
             if (!have) {
                 tiles_to_lds<T, MT, MT>(E, lds, CS, lane);
                 __syncthreads();
-                bool ok = aug_ldl_forward<T, MP, 0, CS, LQRX_DP_BCAST>(lds, lane);
+                bool ok = aug_ldl_forward<T, MP, 0, CS>(lds, lane);
                 if (!ok && info == 0) info = k;
                 __syncthreads();
                 acc Wt[MT][MT], DW[MT][MT];
@@ -1110,11 +1073,9 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-#if LQRX_DP_ROLL_FULL
         if constexpr (FULL && !TV && (64 % (16 * NT)) == 0 && (64 % (16 * MT)) == 0)
-            dp_rollout_full<T, NT, MT, LQRX_DP_KD, LIN, AFF>(a, b, lds, lane);
+            dp_rollout_full<T, NT, MT, LQRX_DP_KD, LIN, AFF>(a, b, lds, lane);   // exact tile grids: register-streamed
         else
-#endif
             dp_rollout<T, NT, MT, TV ? LQRX_DP_TVKD : LQRX_DP_KD, TV, LIN, AFF>(a, b, lds, lane);
     }
 }
@@ -1147,19 +1108,11 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
 // VAR_LIN (lqrx_dp_solve_linear): w = r + Bᵀp (every wave, beside PB), d = Xᵀw (every wave, its
 // own X), p ← q + Aᵀp − Gᵀd for rows 16w…16w+15 (A[:, w], G[:, w] are the wave's own tiles);
 // p is double-buffered in LDS, w and d pass from column to row layout through per-wave slots.
-// The rollout (:66-70): dp_rollout_wg4 on all four waves (an LQRX_WG4_ROLL4=0 build runs the
-// time-invariant one as dp_rollout_full on wave 0: 234.1 vs 224.4 ms at n=64 m=32 N=512 B=8192).
-// The Newton–Schulz step split over the waves (wg4_ns_split, LQRX_WG4_NS_SPLIT=1) measured
-// slower (247.5 vs 234.1 ms: one more barrier per step and 224 B of spills) and is off.
-#ifndef LQRX_WG4_NS_SPLIT
-#define LQRX_WG4_NS_SPLIT 0   // 1: the Newton–Schulz step split over the four waves (m = 32; A/B — measured slower)
-#endif
-#ifndef LQRX_WG4_NS_ONE
-#define LQRX_WG4_NS_ONE 1     // m = 32, time-invariant: the inverse on wave 3, the others' P_ A-parts meanwhile (0: A/B)
-#endif
-#ifndef LQRX_WG4_ROLL4
-#define LQRX_WG4_ROLL4 1      // time-invariant four-wave kernel: the four-wave rollout (0: wave 0 alone, A/B)
-#endif
+// The rollout (:66-70): dp_rollout_wg4 on all four waves.  Was tried: the time-invariant rollout
+// as dp_rollout_full on wave 0 alone, 234.1 vs 224.4 ms at n=64 m=32 N=512 B=8192; the
+// Newton–Schulz step split over the four waves by output tile (wg4_ns_split, m = 32), 247.5 vs
+// 234.1 ms — one more barrier per step and 224 B of spills.  Both forms, and the
+// m = 32 time-invariant inverse in every wave instead of on wave 3, were in the tree up to bba8ceb.
 template <typename T, int MT, int VAR>
 struct Wg4Cfg {
     static constexpr bool TV = (VAR & VAR_TV) != 0, LIN = (VAR & VAR_LIN) != 0;
@@ -1324,50 +1277,6 @@ __device__ __forceinline__ void dp_rollout_wg4(const DpArgs &a, int64_t b, T *ld
         }
         __syncthreads();
     }
-}
-
-// Newton–Schulz on the four waves (MT = 2, ns_refine's step split by output tile): wave w owns
-// tile (w & 1, w >> 1) of R = I − EᵀX and of X + XᵀR; the residual tiles and their magnitude keys
-// meet in LDS (rimg, keys), the new X in ximg — every wave reads the same four keys, so the
-// verdict is workgroup-uniform by construction, and each wave issues a quarter of the refinement
-// (16 instead of 64 MFMAs per step).  X: the full inverse in every wave, in and out.
-template <typename T, int MT>
-__device__ __forceinline__ bool wg4_ns_split(typename Tile<T>::acc (&X)[MT][MT], const T *eimg,
-                                             T *rimg, T *ximg, int *keys, int ld, int w, int lane)
-{
-    static_assert(MT == 2, "one output tile per wave");
-    using acc = typename Tile<T>::acc;
-    const int ti = w & 1, tj = w >> 1;
-    for (int it = 0; it < NsTol<T>::it; ++it) {
-        acc R;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) R[r] = (ti == tj && Tile<T>::row(lane, r) == tcol(lane)) ? (T)1 : (T)0;
-#pragma unroll
-        for (int l = 0; l < MT; ++l)                                               // R = I − EᵀX
-            wg4_mtn<T, true>(R, wg4_tload(eimg + 16 * l + 16 * ti * ld, ld, lane), X[l][tj]);
-        int key = 0;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) key = max(key, mag_key(R[r]));
-        key = wave_max_uniform_i(key);
-        wg4_tstore(rimg + 16 * ti + 16 * tj * ld, ld, R, lane);
-        if (lane == 0) keys[w] = key;
-        __syncthreads();
-        key = max(max(keys[0], keys[1]), max(keys[2], keys[3]));
-        const T rho = (T)(16 * MT) * key_bound(key, (T)0);
-        if (rho <= NsTol<T>::v) return true;                    // X already at working precision
-        if (!(rho < (T)1)) return false;                        // no contraction (or NaN): exact sweep
-        acc Xn = X[ti][tj];
-#pragma unroll
-        for (int l = 0; l < MT; ++l) wg4_mtn<T>(Xn, X[l][ti], wg4_tload(rimg + 16 * l + 16 * tj * ld, ld, lane));
-        wg4_tstore(ximg + 16 * ti + 16 * tj * ld, ld, Xn, lane);   // X + XᵀR
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int j = 0; j < MT; ++j) X[i][j] = wg4_tload(ximg + 16 * i + 16 * j * ld, ld, lane);
-        if (rho <= NsTol<T>::one_step) return true;             // new residual ≤ cond·ρ² ≪ eps
-    }
-    return false;
 }
 
 template <typename T, int MT, int VAR>
@@ -1548,7 +1457,7 @@ __global__ __launch_bounds__(256, 1) void dp_wg4_kernel(const DpArgs a)
         // (time-varying problems keep the inverse in every wave: with Q_k's tiles from HBM added
         // after the barrier the TV / TV+LIN variants measured 73.2 vs 72.7 and 159.5 vs 121.1 ms,
         // profiles/r06/u)
-        constexpr bool NS1 = MT == 2 && !TV && LQRX_WG4_NS_ONE;
+        constexpr bool NS1 = MT == 2 && !TV;
         acc PnA[NS1 ? 3 : 1];
         if constexpr (NS1) {
             if (w != 3) {
@@ -1611,25 +1520,19 @@ __global__ __launch_bounds__(256, 1) void dp_wg4_kernel(const DpArgs a)
                     Xi[i][j] = (T)2 * x1 - Xp[i][j];
                     Xp[i][j] = x1;
                 }
-            if constexpr (MT == 2 && LQRX_WG4_NS_SPLIT) {
-                // split over the waves; the PB image is free after B2 (the exact sweep below, which
-                // reuses it, starts only once every wave has left the refinement)
-                have = wg4_ns_split<T, MT>(Xi, Eim, PBim, PBim + MP * CS, vote, CS, w, lane);
-            } else {
-                acc E[MT][MT];
+            acc E[MT][MT];
 #pragma unroll
-                for (int i = 0; i < MT; ++i)
+            for (int i = 0; i < MT; ++i)
 #pragma unroll
-                    for (int j = 0; j < MT; ++j) E[i][j] = wg4_tload(Eim + 16 * i + 16 * j * CS, CS, lane);
-                have = !a.ns_off && ns_refine<T, MT>(Xi, E, Id, lane);
-                // workgroup-uniform verdict by construction (the branch below holds a barrier): each
-                // wave posts its own Newton–Schulz verdict, every wave takes the AND of all four — no
-                // reliance on the four refinements agreeing bitwise.  (The slots are rewritten only
-                // after this knot's B3, which every wave reaches after reading them.)
-                if (lane == 0) vote[w] = have ? 1 : 0;
-                __syncthreads();
-                have = (vote[0] & vote[1] & vote[2] & vote[3]) != 0;
-            }
+                for (int j = 0; j < MT; ++j) E[i][j] = wg4_tload(Eim + 16 * i + 16 * j * CS, CS, lane);
+            have = !a.ns_off && ns_refine<T, MT>(Xi, E, Id, lane);
+            // workgroup-uniform verdict by construction (the branch below holds a barrier): each
+            // wave posts its own Newton–Schulz verdict, every wave takes the AND of all four — no
+            // reliance on the four refinements agreeing bitwise.  (The slots are rewritten only
+            // after this knot's B3, which every wave reaches after reading them.)
+            if (lane == 0) vote[w] = have ? 1 : 0;
+            __syncthreads();
+            have = (vote[0] & vote[1] & vote[2] & vote[3]) != 0;
         }
         if (!have) {                                       // uniform (k == N − 1, or the vote above)
             if (w == 0) {
@@ -1639,7 +1542,7 @@ __global__ __launch_bounds__(256, 1) void dp_wg4_kernel(const DpArgs a)
                     for (int j = 0; j < MT; ++j)
                         wg4_tstore(aug + 16 * i + 16 * j * CS, CS, wg4_tload(Eim + 16 * i + 16 * j * CS, CS, lane), lane);
                 wsync_w();
-                const bool ok = aug_ldl_forward<T, MP, 0, CS, 0>(aug, lane);
+                const bool ok = aug_ldl_forward<T, MP, 0, CS>(aug, lane);
                 if (lane == 0) *flag = ok ? 1 : 0;
             }
             __syncthreads();
@@ -1763,13 +1666,8 @@ __global__ __launch_bounds__(256, 1) void dp_wg4_kernel(const DpArgs a)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if constexpr (TV || LQRX_WG4_ROLL4) {
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        dp_rollout_wg4<T, MT, TV, LIN>(a, b, lds, w, lane);
-    } else if (w == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        dp_rollout_full<T, NT, MT, LQRX_DP_KD, LIN>(a, b, lds, lane);
-    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    dp_rollout_wg4<T, MT, TV, LIN>(a, b, lds, w, lane);
 }
 
 template <int MT>
@@ -1785,16 +1683,28 @@ static hipError_t launch_wg4(const DpArgs &a, hipStream_t s)
 }
 
 // ------------------------------------------------------------------ launcher
-template <typename T, int NT, int MT, int WAVES = 2, int VAR = 0>
+template <typename T, int NT, int MT, int WAVES, int VAR>
 static hipError_t launch_dp(const DpArgs &a, hipStream_t s);
 
-// time-varying problems take the VAR_TV variant of the same tile grid
-template <typename T, int NT, int MT, int WAVES = 2, int VAR = 0>
+// One tile grid's variants, each at its launch bound (waves per SIMD) — the occupancy table:
+//   grid (16·NT × 16·MT)   plain / LIN / AFF   VAR_TV   VAR_TV|VAR_LIN(|VAR_AFF)
+//   1×1                     2                   2        2
+//   2×1                     2                   2        fp64 1, fp32 2
+//   2×2                     2                   1        1
+//   4×2                     1                   1        1
+template <typename T, int NT, int MT>
 static hipError_t launch_dp_tv(const DpArgs &a, hipStream_t s)
 {
+    // time-invariant (plain, linear terms, affine offset): 2 waves/SIMD up to n ≤ 32, 1 at n ≤ 64.
+    // 2×2 fp64 tiles do not fit 256 registers (≈ 450 live): the 2-wave launch bound compiles
+    // to occupancy 1 (hipcc: "desired occupancy 2, final occupancy 1"; 44–60 B of spills).
+    // Declaring one wave per SIMD instead gave an allocation with 124 B of spills whose launch
+    // ended the process with SIGABRT on the box (round 6, profiles/r06/d) — kept at the launch
+    // bound that passes, see DESIGN §3.1
+    constexpr int WAVES = NT <= 2 ? 2 : 1;
     // 2 waves/SIMD where the time-varying kernel fits 256 registers without spills (tile
     // grids up to 2×1, i.e. n ≤ 32, m ≤ 16 — cfg4's shape), else 1
-    constexpr int TVW = LQRX_DP_TVWAVES ? LQRX_DP_TVWAVES : ((NT <= 2 && MT <= 1) ? 2 : 1);
+    constexpr int TVW = (NT <= 2 && MT <= 1) ? 2 : 1;
     // linear cost terms.  Time-varying: the extra vectors tip cfg4's 2×1 double grid over 256
     // VGPRs (72–91 spilled at 2 waves/SIMD), so VAR_TV|VAR_LIN runs 2 waves/SIMD only on the
     // 1×1 (double) and up to 2×1 (float) grids; time-invariant LIN keeps the plain kernel's
@@ -1802,11 +1712,11 @@ static hipError_t launch_dp_tv(const DpArgs &a, hipStream_t s)
     constexpr int LW = (NT * MT <= (sizeof(T) == 4 ? 2 : 1)) ? 2 : 1;
     // affine offset (needs lin): the launch bounds of the linear-terms variants
     if (a.aff && (a.tv_AB || a.tv_QR)) return launch_dp<T, NT, MT, LW, VAR_TV | VAR_LIN | VAR_AFF>(a, s);
-    if (a.aff) return launch_dp<T, NT, MT, LQRX_DP_AFFWAVES ? LQRX_DP_AFFWAVES : WAVES, VAR_LIN | VAR_AFF>(a, s);
+    if (a.aff) return launch_dp<T, NT, MT, WAVES, VAR_LIN | VAR_AFF>(a, s);
     if (a.lin && (a.tv_AB || a.tv_QR)) return launch_dp<T, NT, MT, LW, VAR_TV | VAR_LIN>(a, s);
     if (a.lin) return launch_dp<T, NT, MT, WAVES, VAR_LIN>(a, s);
     if (a.tv_AB || a.tv_QR) return launch_dp<T, NT, MT, TVW, VAR_TV | LQRX_DP_TVEXTRA>(a, s);
-    return launch_dp<T, NT, MT, WAVES, VAR>(a, s);
+    return launch_dp<T, NT, MT, WAVES, 0>(a, s);
 }
 
 template <typename T, int NT, int MT, int WAVES, int VAR>
@@ -1835,26 +1745,21 @@ hipError_t dp_launch(const DpArgs &a_in, hipStream_t s)
     if (force_big && dp_big_supported(a.n, a.m)) return dp_big_launch(a, s);
     if (a.dtype == 0) {
         if (nt <= 1 && mt <= 1) return launch_dp_tv<double, 1, 1>(a, s);
-        if (nt <= 2 && mt <= 1) return launch_dp_tv<double, 2, 1, LQRX_DP_WAVES, LQRX_DP_VAR>(a, s);
-        // 2×2 fp64 tiles do not fit 256 registers (≈ 450 live): the 2-wave launch bound compiles
-        // to occupancy 1 (hipcc: "desired occupancy 2, final occupancy 1"; 44–60 B of spills).
-        // Declaring one wave per SIMD instead (launch_dp_tv<double, 2, 2, 1>) gave an allocation
-        // with 124 B of spills whose launch ended the process with SIGABRT on the box (round 6,
-        // profiles/r06/d) — kept at the launch bound that passes, see DESIGN §3.1
+        if (nt <= 2 && mt <= 1) return launch_dp_tv<double, 2, 1>(a, s);
         if (nt <= 2 && mt <= 2) return launch_dp_tv<double, 2, 2>(a, s);
         // n = 64, m ∈ {16, 32}: four waves per trajectory — time-invariant or time-varying, with
         // or without linear terms (LQRX_DP_WG4=0 in the environment: the one-wave kernel, for A/B
         // runs and tests)
-        static const bool wg4 = [] { const char *e = std::getenv("LQRX_DP_WG4"); return LQRX_DP_WG4 && !(e && *e == '0'); }();
+        static const bool wg4 = [] { const char *e = std::getenv("LQRX_DP_WG4"); return !(e && *e == '0'); }();
         // (an affine call takes the one-wave kernel below: dp_wg4_kernel has no c_k)
         if (wg4 && !a.aff && a.n == 64 && (a.m == 16 || a.m == 32))
             return a.m == 16 ? launch_wg4<1>(a, s) : launch_wg4<2>(a, s);
-        if (nt <= 4 && mt <= 2) return launch_dp_tv<double, 4, 2, 1>(a, s);   // n ≤ 64: 1 wave/SIMD
+        if (nt <= 4 && mt <= 2) return launch_dp_tv<double, 4, 2>(a, s);
     } else {
         if (nt <= 1 && mt <= 1) return launch_dp_tv<float, 1, 1>(a, s);
         if (nt <= 2 && mt <= 1) return launch_dp_tv<float, 2, 1>(a, s);
         if (nt <= 2 && mt <= 2) return launch_dp_tv<float, 2, 2>(a, s);
-        if (nt <= 4 && mt <= 2) return launch_dp_tv<float, 4, 2, 1>(a, s);    // cfg5: n=64 m=32
+        if (nt <= 4 && mt <= 2) return launch_dp_tv<float, 4, 2>(a, s);    // cfg5: n=64 m=32
     }
     return dp_big_launch(a, s);     // past the register tiles: workgroup per trajectory
 }

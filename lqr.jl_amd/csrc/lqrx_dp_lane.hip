@@ -472,12 +472,6 @@ __device__ __forceinline__ float qbcast(float v)
 template <int R, typename T>
 __device__ __forceinline__ T qfrom(T v) { return qbcast<R | (R << 2) | (R << 4) | (R << 6)>(v); }
 
-#ifndef LQRX_QUAD_RCP
-#define LQRX_QUAD_RCP 1         // m = 1: K = G·rcp(E) instead of the two potrs scalings by rsq(E) (0: A/B)
-#endif
-#ifndef LQRX_QUAD_PB_REPL
-#define LQRX_QUAD_PB_REPL 0     // A/B: 1 = PB = P·B replicated in every lane of the quad (round 4)
-#endif
 // EX (exact shape: n = 4, m = MP, trajectory-contiguous layout): every stride and padding test
 // is a compile-time constant — the rollout's K loads become immediate offsets of one pointer
 template <typename T, int MP, bool SOA, bool LIN = false, bool EX = false>
@@ -548,7 +542,7 @@ __global__ __launch_bounds__(64) void dp_quad_kernel(const DpArgs a)
     for (int i = 0; i < NP; ++i) Pcol[i] = (i < n && q < n) ? ((const T *)a.Qf + tb(nn))[(i + q * n) * es] : (T)0;
     for (int k = N - 1; k >= 1; --k) {   // :61
         T PB[NP][MP];
-        if constexpr (LQRX_QUAD_PB_REPL || sizeof(T) == 4) {
+        if constexpr (sizeof(T) == 4) {
 #pragma unroll
             for (int i = 0; i < NP; ++i)
 #pragma unroll
@@ -632,7 +626,7 @@ __global__ __launch_bounds__(64) void dp_quad_kernel(const DpArgs a)
             for (int p = i + 1; p < MP; ++p) s = fma(-L[p][i], Kq[p], s);
             Kq[i] = s * Linv[i];
         }
-        if constexpr (MP == 1 && sizeof(T) == 8 && LQRX_QUAD_RCP) {
+        if constexpr (MP == 1 && sizeof(T) == 8) {
             // m = 1: potrs is K = G/E.  1/E as v_rcp + one Newton step (≈ 2e-15 relative, rcp_nr)
             // is 3 fp64 instructions where 1/√E (v_rsq + two Newton steps) and the two scalings
             // by it took 9: the backward knot is VALU-issue-bound (≈ 80 VALU per knot on one wave

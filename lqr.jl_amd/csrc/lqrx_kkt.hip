@@ -23,6 +23,12 @@
 #include "lqrx_stage.h"
 #include <hip/hip_runtime.h>
 
+// ---- build switch of this file (diagnostic; the library build does not set it) ----
+#ifndef LQRX_KKT_DMACHECK
+#define LQRX_KKT_DMACHECK 0   // 1: debug build — every staged knot image is compared against a plain
+                              // global read (dma_verify); results unchanged, much slower
+#endif
+
 namespace lqrx {
 
 #define KIDX(i, j, ld) ((i) + (j) * (ld))
@@ -618,9 +624,6 @@ template <int NST> __device__ __forceinline__ void dma_wait_but()
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0) ; lqrx.wait g=1" ::"n"(NST) : "memory");
 }
 
-#ifndef LQRX_KKT_DMACHECK
-#define LQRX_KKT_DMACHECK 0
-#endif
 // Debug build only (-DLQRX_KKT_DMACHECK=1): compare a staged knot image against a plain
 // global read of the same bytes; a mismatch means a staging/wait bug.  Returns 0 if clean.
 __device__ __noinline__ int dma_verify(const KktArgs &a, const KMeta &km, int64_t t, bool live,

@@ -52,11 +52,20 @@
 namespace lqrx {
 namespace {
 
-// timing ablations (tools/tv_ablate.sh builds; results are wrong by design): bit 1 the 16×16
+// ---- build switches of this file (diagnostics for tools/tv_ablate.sh builds; the library build
+// sets none of them) ----
+// KB_ABL: timing ablations of the general forward kernel, results wrong by design: bit 1 the 16×16
 // leaf returns at once, 2 no Schur MFMAs, 4 no forward substitution, 8 no slab stores,
 // 16 no chol_inv at all
 #ifndef KB_ABL
 #define KB_ABL 0
+#endif
+#ifndef KF_NOLEAF
+#define KF_NOLEAF 0          // 1: chol_inv_reg skips its 16×16 leaf factor — timing only, wrong results
+#endif
+#ifndef KU_ABL_MM
+#define KU_ABL_MM 0          // fused stream without its MFMAs: 1 no F (G) products, 2 no C / A — timing
+                             // only, wrong results
 #endif
 
 // KB_PROF builds (timing only): per-phase shader-clock cycles of the forward sweep summed
@@ -1240,48 +1249,23 @@ __global__ void __launch_bounds__(KB_THREADS, 1) kkt_big_hfac_kernel(KhArgs<T> a
 // of conblocks.jl:403-425 (first (0,n,n), interior (n,0,n), last (n,n,0)) and any structure
 // without stage constraints at interior knots.  The backward kernel is shared (same slab).
 
-// tunables (tools/tv_ablate.sh A/B builds override them)
-#ifndef KS_L_KNOTS
-#define KS_L_KNOTS 64
-#endif
-#ifndef KS_PF_SLICES
-#define KS_PF_SLICES 2
-#endif
-#ifndef KS_MIN_BLOCKS
-#define KS_MIN_BLOCKS 4
-#endif
-#ifndef KS_MIN_BLOCKS_F64
-#define KS_MIN_BLOCKS_F64 3          // fp64 tiles need ~1.5x the registers: 4 blocks spill (r03g)
-#endif
-constexpr int KS_L = KS_L_KNOTS;     // knots per Schur unit (one extra A-only pass per unit)
+constexpr int KS_L = 64;             // knots per Schur unit (one extra A-only pass per unit)
 constexpr int KS_HG = KB_WMAX + 4;   // staged H⁻¹ / g row: w columns padded to the slice grid
-constexpr int KS_PF = KS_PF_SLICES;  // k-slices in flight per Schur wave
+constexpr int KS_PF = 2;             // k-slices in flight per Schur wave
+constexpr int KS_MIN_BLOCKS = 4;     // Schur workgroups per CU the fp32 register allocation targets
+constexpr int KS_MIN_BLOCKS_F64 = 3; // fp64 tiles need ~1.5x the registers: 4 blocks spilled (r03g)
 constexpr int KF_W = 4;        // trajectories (waves) per factor workgroup
 constexpr int KF_LU = 68;      // factor LDS image leading dimension
-constexpr int KF_SCR = 4 * KS_HG;                     // per-wave leaf scratch (≥ 64 + 256 + 16)
+// per-wave scratch after the U image and the vector: four H⁻¹ / g rows.  The fused kernel uses it as
+// two areas of 2·KS_HG elements that ping-pong (hcur: knot k+1's H⁻¹|g rows, hoth: the leaf scratch,
+// then knot k+2's rows); the leaf (leaf_chol_inv_e) needs KF_LEAF_SCR elements: the pivot row of U
+// and the scaled row of E, 64 each.  (The round-4 leaf with a separate inverse sweep needed
+// 64 + 256 + 16 = 336, more than the 264 an area holds: with the ping-pong it computed wrong
+// results, ADVICE round 6 — removed after bba8ceb.)
+constexpr int KF_SCR = 4 * KS_HG;
+constexpr int KF_LEAF_SCR = 64 + 64;
+static_assert(KF_LEAF_SCR <= 2 * KS_HG, "the leaf scratch must fit one ping-pong area (hoth) of the fused kernel");
 constexpr int KF_LDS = 64 * KF_LU + 64 + KF_SCR;      // per wave: U image, vector, scratch
-#ifndef KF_OLD_LEAF
-#define KF_OLD_LEAF 0                                 // 1: the 16-lane readlane leaf (A/B builds)
-#endif
-#ifndef KF_INV_SWEEP
-#define KF_INV_SWEEP 0                                // 1: the round-4 leaf inverse sweep (A/B builds)
-#endif
-#ifndef KF_RSQ_RAW
-#define KF_RSQ_RAW 1         // fp32 leaf pivots: v_rsq_f32 without its Newton step (0: A/B)
-#endif
-#ifndef KF_RSQ1_F64
-#define KF_RSQ1_F64 1        // fp64 leaf pivots: v_rsq_f64 + one Newton step instead of two (0: A/B)
-#endif
-#ifndef KU_ZERO_PEEL
-#define KU_ZERO_PEEL 1       // the fused stream's first slice starts its accumulators from a zero C
-                             // operand instead of zeroing 26 tiles by v_mov (0: A/B)
-#endif
-#ifndef KF_LEAF_UNSCALED
-#define KF_LEAF_UNSCALED 0   // 1 (A/B builds): unscaled rows, 1/d and 1/√d formed during the LDS
-                             // round trip — measured slower (fp32 157.4 vs 155.3 ms, fp64 169.1
-                             // vs 167.7 ms configs[4] KKT, profiles r05p): the extra fp64 VALU
-                             // costs more than the rsqrt latency it takes off the chain
-#endif
 
 // image of one knot (elements of T from the knot's base): tiles D, F, B, E, C (256 elements
 // each, lane-major C layout: element 4·lane + r = register r of lane `lane`), then
@@ -1679,80 +1663,34 @@ __device__ __forceinline__ void kf_info(int32_t *info, int64_t t, int v, int kb,
 // U[i][·] (0 at and left of the diagonal) goes through a 64-element LDS row — every row group
 // writes its register holding row i of ITS rows, readers take the group that holds row i — and
 // every lane applies the rank-1 update to its 4 elements unmasked (the zeros confine it to the
-// trailing block).  Then T = U⁻¹ right-looking from the bottom: row k of T = B_k / U_kk is
-// broadcast the same way and B_R −= U[R][k]·T_k with U's strictly-upper columns from an LDS
-// image.  Only the upper triangle of X is read.  q = real pivots (pivots ≥ q are identity
-// padding); returns 1 + the first non-positive pivot, else 0.  scr: KF_SCR elements of LDS.
+// trailing block).  Only the upper triangle of X is read.  q = real pivots (pivots ≥ q are identity
+// padding); returns 1 + the first non-positive pivot, else 0.  scr: KF_LEAF_SCR elements of LDS.
+// Pivot scaling 1/√d.  fp32: v_rsq_f32 alone — the Newton step (4 VALU per pivot, 256 per knot of
+// the fused kernel) buys nothing at the fp32 solve's 1e-4 tolerance (with it: 154.5 vs 153.0 ms,
+// profiles/r06/w).
 __device__ __forceinline__ float leaf_rsq(float d) { return __builtin_amdgcn_rsqf(d); }
 // fp64: v_rsq_f64 (≈ 1e-8 relative, as v_rcp_f64's 4.6e-8) and ONE Newton step — quadratic, so
-// ≈ 1e-16 — where rsqrt_nr takes two (KF_RSQ1_F64 = 0: A/B)
+// ≈ 1e-16 — where rsqrt_nr takes two (two steps: 162.8 vs 160.5 ms, profiles/r06/x_64)
 __device__ __forceinline__ double leaf_rsq(double a)
 {
-    if constexpr (!KF_RSQ1_F64) return rsqrt_nr(a);
     const double y = __builtin_amdgcn_rsq(a);
     const double h = 0.5 * a * y;
     return fma(y, fma(-h, y, 0.5), y);
 }
 
-template <typename T>
-__device__ __forceinline__ int leaf_chol_inv_t(acc_t<T> &X, T *scr, int q, int lane)
-{
-    T *ub = scr, *ut = scr + 64, *ri = ut + 256;        // row buffer, Uᵀ image, 1/U_ii
-    const int c = lane & 15, g = lane >> 4;
-    constexpr bool F64 = sizeof(T) == 8;
-    int bad = 0;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const int gi = F64 ? (i & 3) : (i >> 2), rgi = F64 ? (i >> 2) : (i & 3);
-        const T d = readlane(X[rgi], 16 * gi + i);
-        if (!(d > (T)0) && i < q && !bad) bad = i + 1;
-        const T sc = rsqrt_nr(d);
-        wsync();
-        ub[16 * g + c] = c > i ? X[rgi] * sc : (T)0;
-        if (lane == 0) ri[i] = sc;
-        wsync();
-        const T uc = ub[16 * gi + c];
-        T ur[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) ur[r] = ub[16 * gi + Tile<T>::row(lane, r)];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) X[r] = fma(-ur[r], uc, X[r]);
-        ut[16 * c + i] = uc;                             // U[i][c] (c > i) at [c][i]: Uᵀ, column c
-    }
-    // B = I; k = 15 … 0: T_k = B_k / U_kk (broadcast), B_R −= U[R][k] T_k for R < k
-    acc_t<T> B;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) B[r] = Tile<T>::row(lane, r) == c ? (T)1 : (T)0;
-    T rr[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) rr[r] = ri[Tile<T>::row(lane, r)];
-#pragma unroll
-    for (int k = 15; k >= 0; --k) {
-        const int gk = F64 ? (k & 3) : (k >> 2), rgk = F64 ? (k >> 2) : (k & 3);
-        const T rk = ri[k];
-        wsync();
-        ub[16 * g + c] = B[rgk] * rk;
-        wsync();
-        const T tk = ub[16 * gk + c];
-        T uk[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) uk[r] = ut[16 * k + Tile<T>::row(lane, r)];   // U[R][k], 0 for R ≥ k
-#pragma unroll
-        for (int r = 0; r < 4; ++r) B[r] = fma(-uk[r], tk, B[r]);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) X[r] = B[r] * rr[r];
-    wsync();
-    return bad;
-}
-
-// The same leaf with the inverse carried along (round 5): the factor's row operations — row i
+// The inverse is carried along with the factor (round 5): the factor's row operations — row i
 // scaled by 1/U_ii, rows r > i minus U[i][r]·(scaled row i) — applied to E = I as well turn it
 // into U⁻ᵀ (the operations compose to U⁻ᵀ, since U⁻ᵀ·X = U), so each of the 16 steps broadcasts
-// the scaled row i of E beside the pivot row (one LDS round trip for both) and the separate
-// 16-step back-substitution chain of leaf_chol_inv_t disappears.  T = U⁻¹ = Eᵀ goes through the
-// caller's image Dg (column-major, KF_LU; where leaf_chol_inv_t's caller stored T): E is written
-// transposed and read back as X.  Returns 1 + the first non-positive pivot (< q), else 0.
+// the scaled row i of E beside the pivot row (one LDS round trip for both) and there is no
+// separate 16-step back-substitution chain.  T = U⁻¹ = Eᵀ goes through the caller's image Dg
+// (column-major, KF_LU): E is written transposed and read back as X.  Returns 1 + the first
+// non-positive pivot (< q), else 0.
+// Was tried (build switches up to commit bba8ceb): the round-4 leaf with T = U⁻¹ by a second
+// 16-step sweep from the bottom (leaf_chol_inv_t; chol + inverse 57 k vs 42 k cycles per knot and
+// wave), the general kernel's 16-lane leaf through the LDS image (leaf_chol_inv) in
+// its place, and unscaled rows with 1/d and 1/√d formed during the LDS round trip — fp32 157.4
+// vs 155.3 ms, fp64 169.1 vs 167.7 ms configs[4] KKT (profiles r05p): the extra fp64 VALU costs
+// more than the rsqrt latency it takes off the chain.
 template <typename T>
 __device__ __forceinline__ int leaf_chol_inv_e(acc_t<T> &X, T *scr, T *Dg, int q, int lane)
 {
@@ -1768,28 +1706,7 @@ __device__ __forceinline__ int leaf_chol_inv_e(acc_t<T> &X, T *scr, T *Dg, int q
         const int gi = F64 ? (i & 3) : (i >> 2), rgi = F64 ? (i >> 2) : (i & 3);
         const T d = readlane(X[rgi], 16 * gi + i);
         if (!(d > (T)0) && i < q && !bad) bad = i + 1;
-#if KF_LEAF_UNSCALED
-        // the UNSCALED rows go out at once and 1/d, 1/√d are formed while they cross the LDS:
-        // U[i][r]·U[i][c] = x_r·(x_c/d), the E rows below take (e_i/d), row i itself e_i/√d
-        wsync();
-        ub[16 * g + c] = c > i ? X[rgi] : (T)0;
-        eb[16 * g + c] = E[rgi];
-        wsync();
-        const T id = rcp_full(d), sc = rsqrt_nr(d);
-        const T uc = ub[16 * gi + c], ec = eb[16 * gi + c];
-        T ur[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) ur[r] = ub[16 * gi + Tile<T>::row(lane, r)];
-        const T tu = uc * id, te = ec * id, es = ec * sc;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            X[r] = fma(-ur[r], tu, X[r]);
-            E[r] = Tile<T>::row(lane, r) == i ? es : fma(-ur[r], te, E[r]);
-        }
-#else
-        // fp32 (KF_RSQ_RAW): v_rsq_f32 alone — the Newton step (4 VALU per pivot, 256 per knot of
-        // the fused kernel) buys nothing at the fp32 solve's 1e-4 tolerance; fp64: one step (leaf_rsq)
-        const T sc = (F64 || KF_RSQ_RAW) ? leaf_rsq(d) : rsqrt_nr(d);
+        const T sc = leaf_rsq(d);
         wsync();
         ub[16 * g + c] = c > i ? X[rgi] * sc : (T)0;
         eb[16 * g + c] = E[rgi] * sc;
@@ -1803,7 +1720,6 @@ __device__ __forceinline__ int leaf_chol_inv_e(acc_t<T> &X, T *scr, T *Dg, int q
             X[r] = fma(-ur[r], uc, X[r]);
             E[r] = Tile<T>::row(lane, r) == i ? ec : fma(-ur[r], ec, E[r]);
         }
-#endif
     }
     wsync();
 #pragma unroll
@@ -1846,22 +1762,9 @@ __device__ int chol_inv_reg(acc_t<T> (&X)[10], int nb, int p, T *U, T *scr, int 
     for (int jb = 0; jb < 4; ++jb) {
         if (jb < nb) {
             T *Dg = U + 16 * jb * (1 + KF_LU);
-#if KF_OLD_LEAF
-            tstore(Dg, KF_LU, X[up4(jb, jb)], lane);
-            wsync();
-            const int b = leaf_chol_inv<T>(Dg, KF_LU, min(16, p - 16 * jb), lane);
-            if (b && !bad) bad = 16 * jb + b;
-            wsync();
-            X[up4(jb, jb)] = tload(Dg, KF_LU, lane);
-            (void)scr;
-#elif defined(KF_NOLEAF)
+#if KF_NOLEAF
             const int b = 0;       // timing ablation only: no leaf factor (wrong results)
             (void)scr;
-#elif KF_INV_SWEEP
-            // A/B: the round-4 leaf (inverse by a second 16-step back-substitution sweep)
-            const int b = leaf_chol_inv_t<T>(X[up4(jb, jb)], scr, min(16, p - 16 * jb), lane);
-            if (b && !bad) bad = 16 * jb + b;
-            tstore(Dg, KF_LU, X[up4(jb, jb)], lane);     // T_jj for the inverse assembly's reads
 #else
             const int b = leaf_chol_inv_e<T>(X[up4(jb, jb)], scr, Dg, min(16, p - 16 * jb), lane);
             if (b && !bad) bad = 16 * jb + b;            // (T_jj is in Dg for the inverse assembly)
@@ -2272,37 +2175,14 @@ struct KuArgs {
     int64_t b0, nb, sY, sy, sH, sg, sS;
     int64_t *prof;                           // KB_PROF builds: per-phase cycles (else unused)
 };
-#ifndef KU_PF_SLICES
-#define KU_PF_SLICES 0       // 0: per precision (ku_pf)
-#endif
-#ifndef KU_LEAN
-#define KU_LEAN 1            // H⁻¹/g read at use, λ carried in column layout (fewer live registers)
-#endif
-#ifndef KU_WAVES
-#define KU_WAVES 4           // trajectories (waves) per fused workgroup: 4, or 8 (2 per SIMD in one WG)
-#endif
-#ifndef KU_STAGGER
-#define KU_STAGGER 0         // > 0 (with KU_WAVES 8): waves 4–7 start this many s_sleep units late
-#endif
-#ifndef KU_HG_AHEAD
-#define KU_HG_AHEAD 1        // (KU_LEAN) a slice's H⁻¹/g LDS reads issued one stream step ahead:
-                             // 1 fp64 only, 2 fp32 as well, 0 off (A/B)
-#endif
-#ifndef KU_PP
-#define KU_PP 1              // H⁻¹/g row areas ping-pong: each step stages only knot k+2's rows (0: A/B)
-#endif
-#ifndef KU_HGPF
-#define KU_HGPF 1            // (KU_PP) knot k+2's H / g loads issued before knot k's factor (0: A/B)
-#endif
-#ifndef KU_PRIO
-#define KU_PRIO 1            // the factor phase (latency-bound chain) runs at raised issue priority
-#endif
-// waves per fused workgroup: fp64 stays at 4 (one per SIMD: its LDS and registers)
-template <typename T> constexpr int ku_w() { return sizeof(T) == 4 ? KU_WAVES : 4; }
+// trajectories (waves) per fused workgroup.  Was tried (fp32): 8 waves, two per SIMD in one
+// workgroup, without and with waves 4–7 starting a half knot late — 155.4 / 155.5 vs 154.4 ms
+// configs[4] KKT (profiles/r05/v; in the tree up to bba8ceb)
+constexpr int KU_W = 4;
 // k-slices of Y (of both knots) in flight per wave: fp64 runs one wave per SIMD (512 registers),
 // where a third slice fits and gains (stream 86 k → 82 k cycles per knot, profiles/r05/h; fp32's
-// 2 waves/SIMD spill with three)
-template <typename T> constexpr int ku_pf() { return KU_PF_SLICES ? KU_PF_SLICES : (sizeof(T) == 8 ? 3 : 2); }
+// 2 waves/SIMD spill with three; fp64 with four: 160.9 vs 160.2 ms, profiles/r06/z_64)
+template <typename T> constexpr int ku_pf() { return sizeof(T) == 8 ? 3 : 2; }
 constexpr int KU_LDS = KF_LDS;   // per wave: U / W image, vector, 2 H⁻¹|g rows (also the leaf scratch)
 
 // H⁻¹ (or 1) and g of knot q into one of the wave's LDS rows (0 past w); earlier reads of the
@@ -2375,14 +2255,6 @@ __device__ __forceinline__ void fu_schur2(const Kn &q1, const T *Y1, const T *hg
         for (int v = 0; v < NT; ++v)
             vo2[v] = i16 < q2.p1 - 16 * v ? (uint32_t)((g4 * q2.rows + 16 * v + i16) * (int)TS) : OOB;
     }
-    if constexpr (!KU_ZERO_PEEL) {
-#pragma unroll
-        for (int u = 0; u < NT * NT; ++u) G[u] = tzero<T>();
-#pragma unroll
-        for (int i = 0; i < NT; ++i)
-#pragma unroll
-            for (int j = i; j < NT; ++j) P[up4(i, j)] = tzero<T>();
-    }
     T rp[NB];
 #pragma unroll
     for (int v = 0; v < NB; ++v) rp[v] = (T)0;
@@ -2391,11 +2263,14 @@ __device__ __forceinline__ void fu_schur2(const Kn &q1, const T *Y1, const T *hg
     const int yn2 = q2.rows * q2.w * (int)TS, so2 = 4 * q2.rows * (int)TS;
     const int nks = max(q1.w + 3, q2.w + 3) >> 2;
     constexpr int KU_PF = ku_pf<T>();
-    T f1[KU_PF][NB], f2[KU_PF][NT], h1[KU_PF], c1[KU_PF], h2[KU_PF], c2[KU_PF];
-    // AHEAD: the step of slice s uses the H⁻¹/g values the previous step read and reads those of
-    // slice s + 1, so the LDS round trip is not between a step's start and its first MFMA (rows
-    // are KS_HG = KB_WMAX + 4 long; the read index is clamped to the row)
-    constexpr bool AHEAD = KU_LEAN && (KU_HG_AHEAD == 2 || (KU_HG_AHEAD == 1 && sizeof(T) == 8));
+    T f1[KU_PF][NB], f2[KU_PF][NT];
+    // H⁻¹, g of a slice come straight from the LDS rows (no ring registers: holding them was slower,
+    // 159.0 vs 156.4 ms fp64, profiles/r06/al_64).  AHEAD (fp64; fp32 reads at use — one step ahead
+    // there was 156.4 vs 153.1 ms, profiles/r06/aa): the step of slice s uses the values the
+    // previous step read and reads those of slice s + 1, so the LDS round trip is not between a
+    // step's start and its first MFMA (rows are KS_HG = KB_WMAX + 4 long; the read index is clamped
+    // to the row)
+    constexpr bool AHEAD = sizeof(T) == 8;
     T nh1 = (T)0, ng1 = (T)0, nh2 = (T)0, ng2 = (T)0;
     if constexpr (AHEAD) {
         nh1 = hg1[g4];
@@ -2403,7 +2278,7 @@ __device__ __forceinline__ void fu_schur2(const Kn &q1, const T *Y1, const T *hg
         nh2 = hg2[g4];
         ng2 = hg2[KS_HG + g4];
     }
-    auto load = [&](int s, T (&a1)[NB], T (&a2)[NT], T &hh1, T &gg1, T &hh2, T &gg2) __attribute__((always_inline)) {
+    auto load = [&](int s, T (&a1)[NB], T (&a2)[NT]) __attribute__((always_inline)) {
         const int o1 = s * so1, o2 = s * so2;
         const __amdgpu_buffer_rsrc_t r1 =
             __builtin_amdgcn_make_buffer_rsrc((void *)(yb1 + o1), (short)0, max(yn1 - o1, 0), 0x00020000);
@@ -2415,18 +2290,13 @@ __device__ __forceinline__ void fu_schur2(const Kn &q1, const T *Y1, const T *hg
 #pragma unroll
         for (int v = 0; v < NT; ++v)
             a2[v] = bload<T>(r2, FULL ? vo2[0] + (uint32_t)(16 * v * (int)TS) : vo2[FULL ? 0 : v], 0u);
-        if constexpr (!KU_LEAN) {
-            hh1 = hg1[4 * s + g4];
-            gg1 = hg1[KS_HG + 4 * s + g4];
-            hh2 = hg2[4 * s + g4];
-            gg2 = hg2[KS_HG + 4 * s + g4];
-        }
     };
-    // FIRST (std::true_type, KU_ZERO_PEEL): the stream's first slice — the accumulators start from
-    // a zero C operand (an MFMA inline constant) instead of 26 zeroed tiles
-    auto step = [&](auto first, const T (&a1)[NB], const T (&a2)[NT], T hh1, T gg1, T hh2, T gg2, int s)
-        __attribute__((always_inline)) {
+    // first (std::true_type): the stream's first slice — the accumulators start from a zero C
+    // operand (an MFMA inline constant) instead of 26 tiles zeroed by v_mov (zeroed: 154.1 vs
+    // 153.0 ms fp32, profiles/r06/w)
+    auto step = [&](auto first, const T (&a1)[NB], const T (&a2)[NT], int s) __attribute__((always_inline)) {
         constexpr bool F0 = decltype(first)::value;
+        T hh1, gg1, hh2, gg2;
         if constexpr (AHEAD) {
             hh1 = nh1;
             gg1 = ng1;
@@ -2437,7 +2307,7 @@ __device__ __forceinline__ void fu_schur2(const Kn &q1, const T *Y1, const T *hg
             ng1 = hg1[KS_HG + 4 * sn + g4];
             nh2 = hg2[4 * sn + g4];
             ng2 = hg2[KS_HG + 4 * sn + g4];
-        } else if constexpr (KU_LEAN) {      // H⁻¹, g of the slice straight from LDS (no ring registers)
+        } else {
             hh1 = hg1[4 * s + g4];
             gg1 = hg1[KS_HG + 4 * s + g4];
             hh2 = hg2[4 * s + g4];
@@ -2448,9 +2318,6 @@ __device__ __forceinline__ void fu_schur2(const Kn &q1, const T *Y1, const T *hg
         for (int v = NT; v < NB; ++v) fh1[v] = a1[v] * hh1;
 #pragma unroll
         for (int v = 0; v < NT; ++v) fh2[v] = a2[v] * hh2;
-#ifndef KU_ABL_MM
-#define KU_ABL_MM 0          // timing ablations only (wrong results): 1 no F (G) products, 2 no C / A
-#endif
         if constexpr (KU_ABL_MM != 1) {
 #pragma unroll
         for (int i = 0; i < NT; ++i)
@@ -2475,27 +2342,24 @@ __device__ __forceinline__ void fu_schur2(const Kn &q1, const T *Y1, const T *hg
         for (int v = 0; v < NT; ++v) rp[v] = fma(fh2[v], gg2, rp[v]);
     };
 #pragma unroll
-    for (int u = 0; u < KU_PF; ++u) load(u, f1[u], f2[u], h1[u], c1[u], h2[u], c2[u]);
+    for (int u = 0; u < KU_PF; ++u) load(u, f1[u], f2[u]);
     // branch-free ring (slices past a block's last read 0 and carry h = 0): each step waits
-    // only for its own slice, requested KU_PF steps earlier
-    int s00 = 0;
-    if constexpr (KU_ZERO_PEEL) {            // the first group of KU_PF slices, peeled
-        step(std::true_type{}, f1[0], f2[0], h1[0], c1[0], h2[0], c2[0], 0);
-        load(KU_PF, f1[0], f2[0], h1[0], c1[0], h2[0], c2[0]);
-        __builtin_amdgcn_sched_barrier(0);
+    // only for its own slice, requested KU_PF steps earlier.  The first group of KU_PF slices is
+    // peeled for the zero C operand
+    step(std::true_type{}, f1[0], f2[0], 0);
+    load(KU_PF, f1[0], f2[0]);
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int u = 1; u < KU_PF; ++u) {
-            step(std::false_type{}, f1[u], f2[u], h1[u], c1[u], h2[u], c2[u], u);
-            load(u + KU_PF, f1[u], f2[u], h1[u], c1[u], h2[u], c2[u]);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        s00 = KU_PF;
+    for (int u = 1; u < KU_PF; ++u) {
+        step(std::false_type{}, f1[u], f2[u], u);
+        load(u + KU_PF, f1[u], f2[u]);
+        __builtin_amdgcn_sched_barrier(0);
     }
-    for (int s0 = s00; s0 < nks; s0 += KU_PF) {
+    for (int s0 = KU_PF; s0 < nks; s0 += KU_PF) {
 #pragma unroll
         for (int u = 0; u < KU_PF; ++u) {
-            step(std::false_type{}, f1[u], f2[u], h1[u], c1[u], h2[u], c2[u], s0 + u);
-            load(s0 + u + KU_PF, f1[u], f2[u], h1[u], c1[u], h2[u], c2[u]);
+            step(std::false_type{}, f1[u], f2[u], s0 + u);
+            load(s0 + u + KU_PF, f1[u], f2[u]);
             __builtin_amdgcn_sched_barrier(0);
         }
     }
@@ -2572,19 +2436,12 @@ __device__ __forceinline__ void fu_stream(const int32_t *meta, int kn, const T *
 }
 
 template <typename T, int NT, bool FULL>
-__global__ void __launch_bounds__(64 * ku_w<T>(), sizeof(T) == 4 ? 8 / ku_w<T>() : 1) kb_fuse_mid_kernel(KuArgs<T> a)
+__global__ void __launch_bounds__(64 * KU_W, sizeof(T) == 4 ? 2 : 1) kb_fuse_mid_kernel(KuArgs<T> a)
 {
     extern __shared__ __align__(16) unsigned char kb_lds_raw[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    constexpr int KU_W = ku_w<T>();
     const int64_t tl = (int64_t)blockIdx.x * KU_W + wave;
     if (tl >= a.nb) return;                          // whole wave; no workgroup barriers below
-    if constexpr (KU_W == 8 && KU_STAGGER > 0) {
-        // the two waves sharing a SIMD (w, w + 4) run the same program; offset them so that
-        // one's MFMA-dense streaming overlaps the other's latency-bound factorisation
-        if (wave >= 4)
-            for (int i = 0; i < KU_STAGGER; ++i) __builtin_amdgcn_s_sleep(127);
-    }
     T *U = (T *)kb_lds_raw + wave * KU_LDS, *vb = U + 64 * KF_LU, *hgl = vb + 64;
     const int64_t t = a.b0 + tl, ty = a.yrel ? tl : t;
     const T *Yt = a.Y + ty * a.sY, *yt = a.y + t * a.sy, *Ht = a.H + t * a.sH, *gt = a.g + ty * a.sg;
@@ -2592,13 +2449,13 @@ __global__ void __launch_bounds__(64 * ku_w<T>(), sizeof(T) == 4 ? 8 / ku_w<T>()
     constexpr int PP = 16 * NT;
     int64_t oS = slab_before(a.meta, a.kb);
     acc_t<T> G[16], P[10];                           // P: pivot tiles; W_k after the factor
-    T lam[4][4], x[4], xn[4], lcol[4];               // λ in row layout, or (KU_LEAN) column layout
+    T lam[4][4], x[4], xn[4], lcol[4];               // λ: carried in column layout (lcol), row layout for the reduction
     {
         // the state at kb − 1 (W_{kb−1}, λ_{kb−1}, left in the slab by the general kernel)
         // into the LDS W image the reduction reads
         const int32_t *m = a.meta + 8 * (a.kb - 1);
         kf_resume<T>(P, lam, St + oS - slab_size(r16(m[1]), r16(m[2])), r16(m[2]), r16(m[1]), NT, lane);
-        if constexpr (KU_LEAN) {
+        {
             const T *Sk = St + oS - slab_size(r16(m[1]), r16(m[2]));
             const int P2 = r16(m[2]), Ps = r16(m[1]);
             const int oM = P2 * (P2 + 1) / 2 + Ps * (Ps + 1) / 2 + Ps * P2;
@@ -2614,49 +2471,43 @@ __global__ void __launch_bounds__(64 * ku_w<T>(), sizeof(T) == 4 ? 8 / ku_w<T>()
             for (int j = i; j < NT; ++j) tstore(U + 16 * i + 16 * j * KF_LU, KF_LU, P[up4(i, j)], lane);
     }
     // prologue: knot kb's F, C, d and knot kb+1's A; then F̃_kb, x_kb, P = C_kb + A_{kb+1} − F̃ᵀF̃
-    // H⁻¹/g rows: knot k+1's were staged by the previous stream (as its q2) — KU_PP: the two row
-    // areas ping-pong (hcur: knot k+1's rows, kept through the factor; hoth: the leaf scratch, then
-    // knot k+2's rows) instead of re-staging both knots every step
+    // H⁻¹/g rows: knot k+1's were staged by the previous stream (as its q2) — the two row areas
+    // ping-pong (hcur: knot k+1's rows, kept through the factor; hoth: the leaf scratch, then
+    // knot k+2's rows) instead of re-staging both knots every step (which was 152.0 vs 150.4 ms
+    // fp32, 159.1 vs 156.6 ms fp64, profiles/r06/af)
     T *hcur = hgl + 2 * KS_HG, *hoth = hgl;
     fu_stream<T, NT, FULL>(a.meta, a.kb, Yt, yt, Ht, gt, a.hinv, a.useg, hgl, hgl + 2 * KS_HG, true, G, P, xn, lane);
     wsync();
-    if constexpr (KU_LEAN) col2row<T>(lam, lcol, vb, lane);
+    col2row<T>(lam, lcol, vb, lane);
     fu_reduce<T, NT>(P, G, U, lam, xn, x, lane);
     int info = 0;
 #ifdef KB_PROF
     int64_t kb_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     KB_T0();
 #endif
-    constexpr bool HGPF = KU_PP && KU_HGPF;
     constexpr int NHG = (KS_HG + 63) / 64;
     for (int k = a.kb; k < a.ke; ++k) {
         const int p2 = a.meta[8 * k + 2];
-        // HGPF: knot k+2's H and g requested before the factor (they land under it; the stream
-        // after it only forms H⁻¹ and writes the LDS rows)
+        // knot k+2's H and g requested before the factor (they land under it; the stream after it
+        // only forms H⁻¹ and writes the LDS rows): fp32 149.7 vs 150.8 ms, fp64 neutral (profiles/r06/ag)
         T hv[NHG], gv[NHG];
-        if constexpr (HGPF) {
-            if (k + 1 < a.ke) {
-                const Kn q2 = kn_load(a.meta, k + 2);
+        if (k + 1 < a.ke) {
+            const Kn q2 = kn_load(a.meta, k + 2);
 #pragma unroll
-                for (int u = 0; u < NHG; ++u) {
-                    const int c = lane + 64 * u;
-                    const bool in = c < q2.w;
-                    hv[u] = (in && a.hinv) ? Ht[q2.oH + c] : (T)1;
-                    gv[u] = (in && a.useg) ? gt[q2.og + c] : (T)0;
-                }
+            for (int u = 0; u < NHG; ++u) {
+                const int c = lane + 64 * u;
+                const bool in = c < q2.w;
+                hv[u] = (in && a.hinv) ? Ht[q2.oH + c] : (T)1;
+                gv[u] = (in && a.useg) ? gt[q2.og + c] : (T)0;
             }
         }
-        // C̃_k = chol(P) → P = W_k (:61-62)
-        if constexpr (KU_PRIO) __builtin_amdgcn_s_setprio(2);
-#ifdef KU_NOCHOL
-        const int bad = 0;         // timing ablation only: no factorisation (wrong results)
-        (void)p2;
-#else
+        // C̃_k = chol(P) → P = W_k (:61-62).  The factor phase (a latency-bound chain) runs at raised
+        // issue priority (at normal priority: 156.2 vs 154.4 ms fp32, profiles/r05/v)
+        __builtin_amdgcn_s_setprio(2);
 #ifdef KB_PROF
-        const int bad = chol_inv_reg<T>(P, NT, p2, U, KU_PP ? hoth : hgl, lane, kb_acc + 4);
+        const int bad = chol_inv_reg<T>(P, NT, p2, U, hoth, lane, kb_acc + 4);
 #else
-        const int bad = chol_inv_reg<T>(P, NT, p2, U, KU_PP ? hoth : hgl, lane);
-#endif
+        const int bad = chol_inv_reg<T>(P, NT, p2, U, hoth, lane);
 #endif
         KB_T(0);
         // λ_k = W_kᵀ x_k (:108-116)
@@ -2675,12 +2526,8 @@ __global__ void __launch_bounds__(64 * ku_w<T>(), sizeof(T) == 4 ? 8 / ku_w<T>()
             sacc += __shfl_xor(sacc, 32);
             lc[j] = sacc;
         }
-        if constexpr (KU_LEAN) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) lcol[j] = lc[j];
-        } else {
-            col2row<T>(lam, lc, vb, lane);
-        }
+        for (int j = 0; j < 4; ++j) lcol[j] = lc[j];
         // slab: W_k packed upper (column col at col(col+1)/2: the off-diagonal tiles store
         // unpredicated at a per-lane column base plus immediates; only the diagonal tiles test
         // row ≤ col, the same four lane masks for every tile), λ_k
@@ -2705,7 +2552,7 @@ __global__ void __launch_bounds__(64 * ku_w<T>(), sizeof(T) == 4 ? 8 / ku_w<T>()
             for (int j = 0; j < NT; ++j) Sk[PP * (PP + 1) / 2 + 16 * j + lane] = lc[j];
         }
         if (bad && !info) info = k + 1;
-        if constexpr (KU_PRIO) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
         KB_T(1);
         if (k + 1 < a.ke) {
             // W_k to the LDS image (chol_inv_reg's scratch is free again): no tile is live
@@ -2715,19 +2562,13 @@ __global__ void __launch_bounds__(64 * ku_w<T>(), sizeof(T) == 4 ? 8 / ku_w<T>()
             for (int i = 0; i < NT; ++i)
 #pragma unroll
                 for (int j = i; j < NT; ++j) tstore(U + 16 * i + 16 * j * KF_LU, KF_LU, P[up4(i, j)], lane);
-            if constexpr (KU_PP) {
-                fu_stream<T, NT, FULL>(a.meta, k + 1, Yt, yt, Ht, gt, a.hinv, a.useg, hcur, hoth, false, G, P, xn, lane,
-                                       HGPF ? &hv : nullptr, HGPF ? &gv : nullptr);
-                T *const h = hcur;
-                hcur = hoth;
-                hoth = h;
-            } else {
-                fu_stream<T, NT, FULL>(a.meta, k + 1, Yt, yt, Ht, gt, a.hinv, a.useg, hgl, hgl + 2 * KS_HG, true, G, P,
-                                       xn, lane);
-            }
+            fu_stream<T, NT, FULL>(a.meta, k + 1, Yt, yt, Ht, gt, a.hinv, a.useg, hcur, hoth, false, G, P, xn, lane, &hv, &gv);
+            T *const h = hcur;
+            hcur = hoth;
+            hoth = h;
             wsync();
             KB_T(2);
-            if constexpr (KU_LEAN) col2row<T>(lam, lcol, vb, lane);
+            col2row<T>(lam, lcol, vb, lane);
             fu_reduce<T, NT>(P, G, U, lam, xn, x, lane);
             KB_T(3);
         }
@@ -2750,18 +2591,9 @@ __global__ void __launch_bounds__(64 * ku_w<T>(), sizeof(T) == 4 ? 8 / ku_w<T>()
 // configs[4]'s 8192 waves took 3 rounds instead of 2 — and fp64 to 4.)
 constexpr int KBW_V = 7 * 64;
 constexpr int KBW_W = 2080;
-#ifndef KBW_VC_COLS
-#define KBW_VC_COLS 16
-#endif
-#ifndef KBW_RUN
-#define KBW_RUN 32
-#endif
-// D2 columns the backward kernel holds in registers between its two uses (fp32 96, fp64 32:
-// wider knots hold their first columns and read the rest twice; 2 = off, the array is then a
-// dummy).  KBW_NOHOLD=1 restores the second pass over every D2 column (A/B).
-#ifndef KBW_NOHOLD
-#define KBW_NOHOLD 0
-#endif
+constexpr int KBW_VC = 16;   // columns of Y in flight per lane in the v product
+constexpr int KBW_R = 32;    // column-run elements in flight per lane (t, D2ᵀλ)
+// (32 columns / 64-element runs, fp32: 150.10 / 149.58 vs 149.75 ms — noise, profiles/r06/am)
 __device__ __forceinline__ float rdlane(float v, int l) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l)); }
 __device__ __forceinline__ double rdlane(double v, int l)
 {
@@ -2769,12 +2601,11 @@ __device__ __forceinline__ double rdlane(double v, int l)
     const int lo = __builtin_amdgcn_readlane((int)b, l), hi = __builtin_amdgcn_readlane((int)(b >> 32), l);
     return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned)lo);
 }
-#ifndef KBW_HOLD64
-#define KBW_HOLD64 32        // fp64 D2 columns held (A/B: 64, 96 take the kernel to one wave per SIMD)
-#endif
-template <typename T> constexpr int kbw_hold() { return KBW_NOHOLD ? 2 : sizeof(T) == 4 ? 96 : KBW_HOLD64; }
-constexpr int KBW_VC = KBW_VC_COLS;  // columns of Y in flight per lane in the v product
-constexpr int KBW_R = KBW_RUN;       // column-run elements in flight per lane (t, D2ᵀλ)
+// D2 columns the backward kernel holds in registers between its two uses: wider knots hold their
+// first columns and read the rest twice.  Was tried: fp64 holding 64 or 96 took the kernel to one
+// wave per SIMD (profiles/r05/k64); a second pass over every D2 column instead of holding any
+// (DESIGN §3.9).  Both were build switches up to commit bba8ceb.
+template <typename T> constexpr int kbw_hold() { return sizeof(T) == 4 ? 96 : 32; }
 
 // Σ_{r<n} p[r]·x[r] for a contiguous run p (global) and x (LDS, broadcast reads), n ≤ 128:
 // every load of a 32-element chunk issued before its FMAs (16-B vector loads when `vec`)
@@ -2900,11 +2731,10 @@ __global__ void __launch_bounds__(64 * KF_W) kb_bwd_kernel(KbArgs<T> a, int64_t 
             hc[u] = h;
         }
         wsync();
-        // fp32, w ≤ KBW_HOLD: knot j's D2 rows stay in registers (lane = row) from the v product
+        // w ≤ KH: knot j's D2 rows stay in registers (lane = row) from the v product
         // to D2ᵀλ_{j−1}, so D2 is read once per knot instead of twice
-        T d2[kbw_hold<T>()];
-        constexpr int KH = kbw_hold<T>();
-        const bool hold = KH > 2;                  // columns [0, min(w, KH)) held
+        constexpr int KH = kbw_hold<T>();          // columns [0, min(w, KH)) held
+        T d2[KH];
         Kn qp = qj;
         if (j > 0) {
             qp = kn_load(a.meta, j - 1);
@@ -2937,7 +2767,7 @@ __global__ void __launch_bounds__(64 * KF_W) kb_bwd_kernel(KbArgs<T> a, int64_t 
                 }
             }
             // v = D2 H⁻¹ t = D_{k+1}μ_{k+1} + F_{k+1}λ_{k+1}, lane = row (coalesced columns, 16 in flight)
-            if (hold) {
+            {
                 // every D2 column in flight at once, and kept in registers for D2ᵀλ_{j−1} below
                 // (the second pass over D2 was ~30 % of this kernel's fabric traffic)
                 const int rl = lane < qj.p1 ? lane : 0;
@@ -2945,11 +2775,11 @@ __global__ void __launch_bounds__(64 * KF_W) kb_bwd_kernel(KbArgs<T> a, int64_t 
                     (void *)Yk, (short)0, (int)(qj.rows * qj.w * sizeof(T)), 0x00020000);
                 __builtin_amdgcn_sched_barrier(0);       // not hoisted over the W staging above
 #pragma unroll
-                for (int c = 0; c < kbw_hold<T>(); ++c)      // uniform column offset in soffset
+                for (int c = 0; c < KH; ++c)      // uniform column offset in soffset
                     d2[c] = bload<T>(yrs, (uint32_t)rl * sizeof(T), (uint32_t)((c < qj.w ? c : 0) * qj.rows * sizeof(T)));
                 T s0 = (T)0, s1 = (T)0;
 #pragma unroll
-                for (int c = 0; c < kbw_hold<T>(); c += 2) {  // tbv is 0 past w (set above)
+                for (int c = 0; c < KH; c += 2) {  // tbv is 0 past w (set above)
                     s0 = fma(d2[c], rdlane(tbv[c >> 6], c & 63), s0);
                     s1 = fma(d2[c + 1], rdlane(tbv[(c + 1) >> 6], (c + 1) & 63), s1);
                 }
@@ -2960,26 +2790,6 @@ __global__ void __launch_bounds__(64 * KF_W) kb_bwd_kernel(KbArgs<T> a, int64_t 
 #pragma unroll
                     for (int u = 0; u < KBW_VC; ++u)
                         if (c0 + u < qj.w) s0 = fma(y[u], tb[c0 + u], s0);
-                }
-                vb[lane] = lane < qj.p1 ? s0 + s1 : (T)0;
-            } else {
-                T s0 = (T)0, s1 = (T)0;
-                const int rl = lane < qj.p1 ? lane : 0;
-                for (int c0 = 0; c0 < qj.w; c0 += KBW_VC) {
-                    T y[KBW_VC];
-#pragma unroll
-                    for (int u = 0; u < KBW_VC; ++u) y[u] = c0 + u < qj.w ? Yk[rl + (int64_t)(c0 + u) * qj.rows] : (T)0;
-                    if (c0 + KBW_VC <= qj.w) {
-#pragma unroll
-                        for (int u = 0; u < KBW_VC; u += 2) {
-                            s0 = fma(y[u], tb[c0 + u], s0);
-                            s1 = fma(y[u + 1], tb[c0 + u + 1], s1);
-                        }
-                    } else {
-#pragma unroll
-                        for (int u = 0; u < KBW_VC; ++u)
-                            if (c0 + u < qj.w) s0 = fma(y[u], tb[c0 + u], s0);
-                    }
                 }
                 vb[lane] = lane < qj.p1 ? s0 + s1 : (T)0;
             }
@@ -3025,7 +2835,7 @@ __global__ void __launch_bounds__(64 * KF_W) kb_bwd_kernel(KbArgs<T> a, int64_t 
             lb[lane] = -nl;
             wsync();
         }
-        if (hold && j > 0) {
+        if (j > 0) {
             // D2ᵀλ_{j−1} from the held rows: per-lane products, column sums by a 16-column LDS
             // transpose (row stride 17: conflict-free both ways) and two lane exchanges; the sums
             // land in tb (dead since the v product).  W_{j−1} (wl) is dead once λ_{j−1} is formed.
@@ -3033,7 +2843,7 @@ __global__ void __launch_bounds__(64 * KF_W) kb_bwd_kernel(KbArgs<T> a, int64_t 
             T *red = wl;
             const int cc = lane & 15, q4 = lane >> 4;
 #pragma unroll
-            for (int c0 = 0; c0 < kbw_hold<T>(); c0 += 16) {
+            for (int c0 = 0; c0 < KH; c0 += 16) {
                 if (c0 < qj.w) {
 #pragma unroll
                     for (int i = 0; i < 16; ++i) red[lane * 17 + i] = d2[c0 + i] * lr;
@@ -3058,7 +2868,7 @@ __global__ void __launch_bounds__(64 * KF_W) kb_bwd_kernel(KbArgs<T> a, int64_t 
         for (int u = 0; u < 2; ++u) {
             const int c = lane + 64 * u;
             if (c < qj.w) {
-                const T sd = j > 0 ? ((hold && c < KH) ? tb[c] : dot_run<T>(Yk + (int64_t)c * qj.rows, lb, qj.p1, vs)) : (T)0;
+                const T sd = j > 0 ? (c < KH ? tb[c] : dot_run<T>(Yk + (int64_t)c * qj.rows, lb, qj.p1, vs)) : (T)0;
                 const T res = tc[u] + sd + graw[u];
                 if (a.hfac) tb[c] = res;
                 else dzt[qj.og + c] = -(res * hc[u]);
@@ -3307,12 +3117,7 @@ hipError_t kb_launch_t(const KktArgs &a, const KbPlan &P, hipStream_t s)
         kf.fz1 = P.fuse ? P.mid1 : 0;
     }
     KuArgs<T> ku{};
-    constexpr int KU_W = ku_w<T>();
-#ifdef KU_SOLO
-    const size_t lfu = std::max((size_t)KU_W * KU_LDS * sizeof(T), (size_t)96 * 1024);   // 1 WG per CU (A/B only)
-#else
     const size_t lfu = (size_t)KU_W * KU_LDS * sizeof(T);
-#endif
     if (P.fuse) {
         ku.Y = P.hfac ? Z : (const T *)a.Y; ku.y = (const T *)a.y; ku.H = (const T *)a.H;
         ku.g = P.hfac ? gz : (const T *)a.g;

@@ -31,21 +31,21 @@
 #include <cstdlib>
 #include <type_traits>
 
-namespace lqrx {
-namespace fil {
-
+// ---- build switches of this file (diagnostics; the library build sets none of them) ----
 #ifndef LQRX_FIL_ABL
 #define LQRX_FIL_ABL 0   // ablation builds for tools/ only (bits: 1 forward sweep alone, 2 Schur
                          // from one column, 4 no F̃ recompute, 8 primal without Yᵀm, 16 no
                          // hand-placed VMEM waits, 32 no forward slab stores, 64 no δz/λ
                          // stores — timing bounds only, results wrong)
 #endif
-#ifndef LQRX_FIL_RING
-#define LQRX_FIL_RING 1  // layout-0 δz/λ of interior knots through the LDS output ring (0: direct stores)
+#ifndef LQRX_FIL_WAIT_SLACK
+#define LQRX_FIL_WAIT_SLACK 0   // test-only negative control (tests/test_isa_guards.py): loosens every
+                                // hand vmcnt bound of vm_wait by that many ops — results may be wrong
 #endif
-#ifndef LQRX_FIL_N12
-#define LQRX_FIL_N12 1   // 12-byte LDS-DMA pieces for the short chunks (0: dwords only)
-#endif
+
+namespace lqrx {
+namespace fil {
+
 constexpr int Z(int x) { return x > 0 ? x : 1; }
 constexpr int tri(int x) { return x * (x + 1) / 2; }
 
@@ -80,7 +80,7 @@ struct Shape {
     // Y goes in 16-byte pieces when every knot's Y block has an even length (then every
     // knot offset and the trajectory stride are even); the short y/H/g chunks in dwords
     static constexpr bool WIDE_Y = (LY<F>() % 2 == 0) && (LY<I>() % 2 == 0) && (LY<L>() % 2 == 0);
-    static constexpr int nsplit(int L) { return LQRX_FIL_N12 ? (8 * L) / 12 + ((8 * L) % 12) / 4 : 2 * L; }   // = Split<L>::instrs
+    static constexpr int nsplit(int L) { return (8 * L) / 12 + ((8 * L) % 12) / 4; }   // = Split<L>::instrs
     // SOA: one 16-B-per-lane DMA moves two element rows (2 × 64 doubles)
     static constexpr int rows2(int L) { return (L + 1) / 2; }
     template <class C> static constexpr int Dmin()   // DMA instructions of a forward restage
@@ -105,7 +105,7 @@ struct Shape {
     // (SOA: [element row][64 lanes] images, rows rounded up to even — the DMA moves row pairs)
     static constexpr int sb(int L)
     {
-        return SOA ? 8 * (2 * rows2(L)) : LQRX_FIL_N12 ? 16 * ((8 * L) / 12) + 4 * (((8 * L) % 12) / 4) : 8 * L;
+        return SOA ? 8 * (2 * rows2(L)) : 16 * ((8 * L) / 12) + 4 * (((8 * L) % 12) / 4);
     }
     static constexpr int OFF_y = 64 * (SOA ? sb(LYm) : 8 * LYm);
     static constexpr int OFF_H = OFF_y + 64 * mx3<sb(Ly<F>()), sb(Ly<I>()), sb(Ly<L>())>();
@@ -261,7 +261,7 @@ template <int L, bool WIDE> struct Pat {
 // A = [t][n12][16 B] (12 valid) and B = [t][n4][4 B].  The reader (SImg) reassembles a
 // double from its two dwords.  5 doubles cost 3 + 1 instructions instead of 10 dwords.
 template <int L> struct Split {
-    static constexpr int B = 8 * L, n12 = LQRX_FIL_N12 ? B / 12 : 0, n4 = (B - 12 * n12) / 4;
+    static constexpr int B = 8 * L, n12 = B / 12, n4 = (B - 12 * n12) / 4;
     static constexpr int bytesA = 64 * 16 * n12;
     static constexpr int lane_bytes = 16 * n12 + 4 * n4;       // LDS bytes per trajectory
     static constexpr int instrs = n12 + n4;
@@ -647,9 +647,6 @@ __device__ __forceinline__ double bload(rsrc_t r, uint32_t vo, uint32_t so)
 // tests/isa_vmcnt.py can check N against the compiled instruction stream (N > 0 needs a G).
 // LQRX_FIL_WAIT_SLACK (test-only negative control, never in the library build) loosens every
 // bound by that many ops.
-#ifndef LQRX_FIL_WAIT_SLACK
-#define LQRX_FIL_WAIT_SLACK 0
-#endif
 template <int N, int G = 0> __device__ __forceinline__ void vm_wait()
 {
     static_assert(N <= 0 || G > 0, "a hand vmcnt bound names its target DMA group");
@@ -1345,7 +1342,7 @@ __global__ __launch_bounds__(64) void kkt_fil_kernel(const KktArgs a, double *__
     __shared__ __attribute__((aligned(16))) double ost[S::SOA ? 1 : 64 * (S::WOUT + S::LOUT)];
     // the layout-0 output ring (two group images), where the static LDS allows it
     __shared__ __attribute__((aligned(16))) uint32_t dpad[64];   // stage_fill's target
-    constexpr bool RING = !S::SOA && LQRX_FIL_RING &&
+    constexpr bool RING = !S::SOA &&
                           (3 * S::BUF + 3 * SLB<S> + 64 * (S::WOUT + S::LOUT) + 2 * or_doubles<S>()) * 8 + 256 <=
                               160 * 1024;
     __shared__ __attribute__((aligned(16))) double oring[RING ? 2 * or_doubles<S>() : 1];
@@ -1791,8 +1788,8 @@ __global__ __launch_bounds__(64) void kkt_fild_kernel(const KktArgs a, double *_
     using L = typename S::L;
     __shared__ __attribute__((aligned(16))) double ost[S::SOA ? 1 : 64 * (S::WOUT + S::LOUT)];
     const int N = a.N;                                          // ≥ 4 (host-checked)
-    // LPW live trajectories per wave (fild_lpw: 32 on small layout-0 batches, the other lanes
-    // shadow the last live one); layout 1 keeps 64 (gld's row base)
+    // LPW live trajectories per wave (the host's FILD_LPW; below 64 the other lanes shadow the
+    // last live one); layout 1 keeps 64 (gld's row base)
     const int LPW = S::SOA ? 64 : a.lpw;
     const int64_t t0 = (int64_t)blockIdx.x * LPW;
     Ctx<S> c;
@@ -1907,20 +1904,15 @@ __global__ __launch_bounds__(64) void kkt_fild_kernel(const KktArgs a, double *_
     if (a.info && c.live) a.info[t0 + c.lane] = info;
 }
 
-// live trajectories per wave of the direct kernel.  A/B (LQRX_FILD_LPW=32: a layout-0 batch
-// ≤ 32768 runs 32 per wave, twice the waves) measured slower at B = 16384 — (6,2,101) 2.24 →
+// live trajectories per wave of the direct kernel (KktArgs::lpw).  Was tried: 32 per wave (twice
+// the waves) for a layout-0 batch ≤ 32768 measured slower at B = 16384 — (6,2,101) 2.24 →
 // 2.60 ms, (8,4,101) 6.24 → 7.75, (5,2,101) 1.38 → 1.54, DoubleIntegrator(3) 2.64 → 2.91
 // (profiles/r05/r): the kernel is bound by its waves' instruction issue, not by loads in flight
-#ifndef LQRX_FILD_LPW
-#define LQRX_FILD_LPW 64
-#endif
-template <class S> int fild_lpw(const KktArgs &a)
-{
-    return (!S::SOA && a.batch <= 32768) ? LQRX_FILD_LPW : 64;
-}
+// (the build switch for it was removed after bba8ceb)
+constexpr int FILD_LPW = 64;
 template <class S> size_t slab_bytes(const KktArgs &a)
 {
-    const int lpw = fild_lpw<S>(a);   // (also the LDS-ring kernel's bound at 64: ≥ its need)
+    const int lpw = FILD_LPW;   // (also the LDS-ring kernel's bound at 64: ≥ its need)
     const size_t Bp = (((size_t)a.batch + lpw - 1) / lpw) * 64;   // wave-major slab, 64 lanes/wave
     // (+1 KiB: the backward slab DMA of the last knot may read up to 512 B past its chunk)
     return Bp * (size_t)a.N * S::SLOT * sizeof(double) + 1024;
@@ -1934,7 +1926,7 @@ hipError_t launch(const KktArgs &a, hipStream_t s)
     if (e != hipSuccess) return e;
     if constexpr (DIRECT) {
         KktArgs b = a;
-        b.lpw = fild_lpw<S>(a);
+        b.lpw = FILD_LPW;
         dim3 grid((unsigned)((a.batch + b.lpw - 1) / b.lpw)), block(64);
         hipLaunchKernelGGL((kkt_fild_kernel<S>), grid, block, 0, s, b, (double *)sc.p);
     } else {

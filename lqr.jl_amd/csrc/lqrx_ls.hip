@@ -36,10 +36,7 @@ constexpr int LS_BIG_MAX_NM = 1024; // H in global scratch (the "big" path): blo
 constexpr int LS_PB = 16;           // big path: max panel rows factored in LDS per pass (the host
                                     // halves it until the panel fits the LDS budget)
 constexpr size_t LS_LDS_CAP = 163840;
-#ifndef LQRX_LS_PNL
-#define LQRX_LS_PNL 4
-#endif
-constexpr int LS_PNL = LQRX_LS_PNL;  // LDS path: potrf panel rows per barrier pair
+constexpr int LS_PNL = 4;            // LDS path: potrf panel rows per barrier pair
 
 // order one wave's LDS accesses across lanes (a wave executes LDS ops in order; this stops
 // the compiler from moving them across and waits for the writes)

@@ -27,16 +27,6 @@
 #include <cmath>
 #include <vector>
 
-#ifndef LQRX_SQP_YSTAGE
-#define LQRX_SQP_YSTAGE 1   // stage the expand kernel's Y blocks through LDS (0: direct stores, A/B)
-#endif
-#ifndef LQRX_SQP_ETPB
-#define LQRX_SQP_ETPB 1     // expand kernel: waves (trajectories) per workgroup (A/B: 1 ≥ 2 > 4)
-#endif
-#ifndef LQRX_SQP_EWAVES
-#define LQRX_SQP_EWAVES 1   // expand kernel: minimum waves per SIMD the register allocation targets
-#endif
-
 namespace lqrx {
 namespace sqp {
 
@@ -410,10 +400,12 @@ __device__ __forceinline__ void expand_knot(const Args &A, int t, int k, double 
 // The 64 knots a wave expands at once own one contiguous run of Y (consecutive knot blocks,
 // Dims::oY).  Written lane-per-knot, every store instruction touches 64 blocks RM·W·8 bytes
 // apart; staged, the blocks are built in the wave's LDS image and the run is copied out in
-// 512-B rows.  Staged when the image fits 20 KB per wave.
+// 512-B rows.  Staged when the image fits 20 KB per wave (direct stores for every model were the
+// A/B alternative; staging was kept).
 template <class M> constexpr int yimg_doubles() { return 64 * (2 * M::NX + M::PK) * (M::NX + M::NU); }
-template <class M> constexpr bool y_staged() { return LQRX_SQP_YSTAGE && yimg_doubles<M>() * 8 <= 20480; }
-constexpr int ETPB = LQRX_SQP_ETPB;                       // trajectories (waves) per expand workgroup
+template <class M> constexpr bool y_staged() { return yimg_doubles<M>() * 8 <= 20480; }
+constexpr int ETPB = 1;   // trajectories (waves) per expand workgroup (was tried: 1 ≥ 2 > 4); the
+                          // kernel's register allocation targets one wave per SIMD
 
 __device__ inline void wave_sync()
 {
@@ -422,7 +414,7 @@ __device__ inline void wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
-template <class M> __global__ __launch_bounds__(64 * ETPB, LQRX_SQP_EWAVES) void sqp_expand_kernel(const Args A)
+template <class M> __global__ __launch_bounds__(64 * ETPB, 1) void sqp_expand_kernel(const Args A)
 {
     using D = Dims<M>;
     constexpr bool ST = y_staged<M>();

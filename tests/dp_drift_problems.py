@@ -1,6 +1,5 @@
 """Problem families that walk the Riccati kernels' Newton–Schulz acceptance rule through all of
-its paths, and a numpy restatement of that rule (lqrx_dp.hip: NsTol / ns_round / ns_refine, the
-four-wave copy wg4_ns_split).  A plain module: tests/test_dp_ns_census.py pins the paths the
+its paths, and a numpy restatement of that rule (lqrx_dp.hip: NsTol / ns_round / ns_refine).  A plain module: tests/test_dp_ns_census.py pins the paths the
 committed seeds reach (no device), tests/test_dp_ns_regimes_gpu.py runs the kernels on them.
 
 Every family starts from lqrx.random_batch (the library's generator: R = I + GGᵀ/m, Qf = 10 Q)

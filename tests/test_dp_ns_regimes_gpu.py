@@ -1,5 +1,5 @@
-"""GPU: the Riccati kernels' Newton–Schulz acceptance (lqrx_dp.hip NsTol / ns_round / ns_refine,
-wg4_ns_split and the AND-ed verdicts of dp_wg4_kernel) on inputs that take every path of the rule
+"""GPU: the Riccati kernels' Newton–Schulz acceptance (lqrx_dp.hip NsTol / ns_round / ns_refine
+and the AND-ed verdicts of dp_wg4_kernel) on inputs that take every path of the rule
 — not only the exact sweep and the round-0 accept at the rounding floor that the rest of the suite
 reaches.  Problems and the census of paths: tests/dp_drift_problems.py, tests/test_dp_ns_census.py.
 

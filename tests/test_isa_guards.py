@@ -168,11 +168,11 @@ def test_dp_rollout_hand_waits_by_issue_order(asm_of):
     assert DP_HEADLINE in hand and hand[DP_HEADLINE]["hand_waits"] > 0, sorted(hand)
     assert len([k for k in hand if "dp_riccati_kernel" in k]) >= 6, sorted(hand)   # fp64 / fp32 × grids
     # every wg4 instance is analysed (m = 16 / 32 × plain, TV, LIN, TV|LIN); since round 6 their
-    # rollout is dp_rollout_wg4 on all four waves (compiler-tracked loads), so any wg4 function that
-    # still issues asm loads (an LQRX_WG4_ROLL4=0 build: dp_rollout_full on wave 0) must hand-wait
+    # rollout is dp_rollout_wg4 on all four waves (compiler-tracked loads) and the build that ran
+    # dp_rollout_full on wave 0 alone is gone, so no wg4 function issues asm loads any more
     assert len([k for k in stats if WG4.match(k)]) >= 8, sorted(stats)
     wg4 = [k for k in hand if WG4.match(k)]
-    assert all(hand[k]["hand_waits"] > 0 for k in wg4), sorted(hand)
+    assert wg4 == [], wg4
     assert not findings, findings[:5]
 
 

@@ -5,7 +5,10 @@
 # others are linked from the in-tree build.  Arguments: name:defines ...  Defaults (SRC =
 # lqrx_dp.hip): the time-varying DP ablation of profiles/r02/dp_tv_ablation_r02.txt —
 #   TVABL bit 1: Q_k re-read from knot 1 (cache-resident); bit 2: A_k/B_k/R_k likewise
-#   TVEXTRA 4: no rollout (VAR_NOROLL);  TVKD / TVAD: rollout prefetch depths
+#   TVEXTRA 4: no rollout (VAR_NOROLL)
+# The switches a -D can set are the diagnostics listed in tests/test_build_switches.py (KB_ABL,
+# KB_PROF, KF_NOLEAF, KU_ABL_MM, LQRX_FIL_ABL, LQRX_DP_TVABL, LQRX_DP_TVEXTRA, LQRX_KKT_DMACHECK);
+# the settled A/B alternatives of rounds 2–6 are no longer in the sources (last at commit bba8ceb).
 set -e
 cd "$(dirname "$0")/../lqr.jl_amd/csrc"
 SRC=${SRC:-lqrx_dp.hip}

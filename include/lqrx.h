@@ -46,9 +46,9 @@ extern "C" {
                                    KKT layout 1 for every structure (staged);
                                    lqrx_dp_compute_ctg[_host] (per-knot surface);
                                 5: lqrx_*_host_devices (one call sharded over GPUs);
-                                   lqrx_dp_solve_affine[_host] are additive to ABI 5 (no
-                                   existing signature or struct changed, the number stays 5):
-                                   detect them by symbol (dlsym) */
+                                   lqrx_dp_solve_affine[_host] and lqrx_dp_solve_cross[_host]
+                                   are additive to ABI 5 (no existing signature or struct
+                                   changed, the number stays 5): detect them by symbol (dlsym) */
 
 #define LQRX_F64 0
 #define LQRX_F32 1
@@ -166,8 +166,8 @@ int lqrx_dp_solve_linear_host(const lqrx_dp_desc *desc, const void *A, const voi
  * DP path with affine dynamics  x_{k+1} = A_k x_k + B_k u_k + c_k  — what a linearisation
  * about a non-equilibrium trajectory yields (reference tracking, the defect of a
  * multiple-shooting / SQP iterate, a gravity or disturbance feed-through); together with
- * the linear cost terms above this is the whole LQ subproblem of an iLQR / SQP / MPC
- * caller.  With V_{k+1}(x) = ½xᵀP x + pᵀx, E = R_k + BᵀPB, G = BᵀPA:
+ * the linear cost terms above and the cost cross term of lqrx_dp_solve_cross below this is
+ * the LQ subproblem of an iLQR / SQP / MPC caller.  With V_{k+1}(x) = ½xᵀP x + pᵀx, E = R_k + BᵀPB, G = BᵀPA:
  *   p̃   = p_{k+1} + P_{k+1} c_k
  *   K_k = E⁻¹G                     (K, P and info do not depend on c, q, r)
  *   d_k = E⁻¹(r_k + Bᵀp̃)          p_k = q_k + Aᵀp̃ − Gᵀd_k          P_k = Q_k + AᵀPA − GᵀK_k
@@ -197,6 +197,47 @@ int lqrx_dp_solve_affine_host(const lqrx_dp_desc *desc, const void *A, const voi
                               const void *c, const void *Q, const void *R, const void *Qf,
                               const void *x0, const lqrx_dp_linear *lin, void *K, void *P,
                               void *X, void *U, int32_t *info);
+
+/* ------------------------------------------------------------------------------------
+ * DP path with a cost cross term: stage cost ½xᵀQ_k x + uᵀM_k x + ½uᵀR_k u + q_kᵀx + r_kᵀu —
+ * the Q_ux of an iLQR / DDP backward pass, a cost on an output y = Cx + Du, a cost
+ * discretised with the dynamics, a problem after the feedback pre-transformation u = ũ − Fx.
+ * The affine recursion above changes in one place, G:
+ *   E   = R_k + BᵀPB                    (unchanged: info does not depend on M)
+ *   G   = BᵀPA + M_k
+ *   K_k = E⁻¹G        d_k = E⁻¹(r_k + Bᵀp̃)        p̃ = p_{k+1} + P_{k+1} c_k
+ *   P_k = Q_k + AᵀPA − GᵀK_k            p_k = q_k + Aᵀp̃ − Gᵀd_k
+ *   rollout unchanged: u_k = −K_k x_k − d_k,  x_{k+1} = A_k x_k + B_k u_k + c_k
+ * The problem is convex when the joint block [Q_k M_kᵀ; M_k R_k] is positive semidefinite;
+ * info is, as everywhere, the first knot whose E is not positive definite.  Same descriptor,
+ * inputs and outputs as lqrx_dp_solve_affine plus
+ *   M   m·n·batch, column-major m×n per trajectory (the shape of K_k), or m·n·(N−1)·batch when
+ *       knot_stride_QR = 1 (knot k at k−1: M is a cost term and follows Q and R, as q and r
+ *       do); desc.layout applies to it as to every array.
+ * c and lin are required with all pointers non-NULL, as in lqrx_dp_solve_affine: a caller
+ * without an offset or without linear cost terms passes zeros.  One kernel family serves the
+ * entry, so a caller with only a cross term pays for the linear and affine work as well; a
+ * leaner variant without them is a possible follow-up.  All-zero M gives the
+ * lqrx_dp_solve_affine results.
+ * Error codes follow the argument position: desc −1, A −2, B −3, c −4, Q −5, R −6, M −7,
+ * Qf −8, x0 −9, lin or one of its members −10, K −11, P −12, X −13, U −14, decided before the
+ * device is touched; batch = 0 returns 0.
+ * Every (n, m, dtype, layout, knot stride, p_mode) lqrx_dp_solve_affine accepts is accepted,
+ * with its kernel routing: n ≤ 4 the lane-per-trajectory kernel, fp64 n = 64 the one-wave
+ * register-tiled kernel, past the register tiles the workgroup-per-trajectory kernel.
+ * Out of scope: there is no _host_devices twin, no lqrx_dp_compute_ctg with a cross term, and
+ * the constant of the value function is not formed.  Additive to ABI 5: detect by symbol.
+ * ------------------------------------------------------------------------------------ */
+int lqrx_dp_solve_cross(const lqrx_dp_desc *desc, const void *A, const void *B, const void *c,
+                        const void *Q, const void *R, const void *M, const void *Qf,
+                        const void *x0, const lqrx_dp_linear *lin, void *K, void *P, void *X,
+                        void *U, int32_t *info, void *stream);
+
+/* host pointers in lin and everywhere else: H2D, solve, D2H, synchronous */
+int lqrx_dp_solve_cross_host(const lqrx_dp_desc *desc, const void *A, const void *B,
+                             const void *c, const void *Q, const void *R, const void *M,
+                             const void *Qf, const void *x0, const lqrx_dp_linear *lin, void *K,
+                             void *P, void *X, void *U, int32_t *info);
 
 /* ------------------------------------------------------------------------------------
  * KKT path: one inner solve of CholeskySolver._solve!(solver)

@@ -231,27 +231,40 @@ function solve_linear!(sol::LQRSolution{T}, d::Array{T,3}, p::Array{T}, solver::
 end
 
 """
-    solve_linear!(sol, d, p, solver, prob, q, r, qf, c)
+    solve_linear!(sol, d, p, solver, prob, q, r, qf, c; M = nothing)
 
 The same solve with affine dynamics x_{k+1} = A x_k + B u_k + c (c: n×batch, the constant
 term of a linearisation about a trajectory that is not an equilibrium); q, r, qf may be
 zeros.  lqrx_dp_solve_affine_host (c is argument 4, after A and B).
+
+With the keyword `M` (m×n×batch, one column-major m×n block per trajectory) the stage cost gains
+the cross term uᵀM x, G = BᵀPA + M: lqrx_dp_solve_cross_host (M is argument 7, after Q and R);
+c may be zeros.  Both entries are additive to ABI 5 and are bound by symbol.
 """
 function solve_linear!(sol::LQRSolution{T}, d::Array{T,3}, p::Array{T}, solver::DPSolver{T},
                        prob::LQRBatch{T}, q::Matrix{T}, r::Matrix{T}, qf::Matrix{T},
-                       c::Matrix{T}) where T
+                       c::Matrix{T}; M::Union{Nothing,Array{T,3}} = nothing) where T
     n, m, N = solver.n, solver.m, solver.N
     batch = size(prob.A, 3)
     size(c) == (n, batch) || throw(ArgumentError("c must be n×batch"))
+    M === nothing || size(M) == (m, n, batch) || throw(ArgumentError("M must be m×n×batch"))
     all_P = ndims(sol.P) == 4
     desc = Ref(DpDesc(n, m, N, dtypecode(T), batch, 0, all_P ? 1 : 0, 0, 0))
-    GC.@preserve prob sol d p q r qf c begin
+    GC.@preserve prob sol d p q r qf c M begin
         lin = Ref(DpLinear(pointer(q), pointer(r), pointer(qf), pointer(d), pointer(p)))
-        rc = ccall((:lqrx_dp_solve_affine_host, liblqrx), Cint,
-                   (Ref{DpDesc}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ref{DpLinear},
-                    Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{Int32}),
-                   desc, prob.A, prob.B, c, prob.Q, prob.R, prob.Qf, prob.x0, lin,
-                   sol.Kdata, sol.P, sol.Xdata, sol.Udata, sol.info)
+        if M === nothing
+            rc = ccall((:lqrx_dp_solve_affine_host, liblqrx), Cint,
+                       (Ref{DpDesc}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ref{DpLinear},
+                        Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{Int32}),
+                       desc, prob.A, prob.B, c, prob.Q, prob.R, prob.Qf, prob.x0, lin,
+                       sol.Kdata, sol.P, sol.Xdata, sol.Udata, sol.info)
+        else
+            rc = ccall((:lqrx_dp_solve_cross_host, liblqrx), Cint,
+                       (Ref{DpDesc}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T},
+                        Ref{DpLinear}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{Int32}),
+                       desc, prob.A, prob.B, c, prob.Q, prob.R, M, prob.Qf, prob.x0, lin,
+                       sol.Kdata, sol.P, sol.Xdata, sol.Udata, sol.info)
+        end
     end
     return check(rc)
 end

@@ -154,15 +154,15 @@ hipError_t dp_launch_soa_staged(const lqrx::DpArgs &a, hipStream_t s)
 {
     const int64_t B = a.batch, n = a.n, m = a.m, N = a.N, es = dsize(a.dtype);
     const int64_t kAB = a.tv_AB ? N - 1 : 1, kQR = a.tv_QR ? N - 1 : 1;
-    // inputs A B Q R Qf x0 [q r qf [c]], outputs K P X U [d p]
-    const int nin = a.aff ? 10 : (a.lin ? 9 : 6), nout = a.lin ? 6 : 4;
-    const int64_t S_in[10] = {n * n * kAB, n * m * kAB, n * n * kQR, m * m * kQR, n * n, n,
-                              n * kQR, m * kQR, n, n * kAB};
+    // inputs A B Q R Qf x0 [q r qf [c [M]]], outputs K P X U [d p]
+    const int nin = a.cross ? 11 : (a.aff ? 10 : (a.lin ? 9 : 6)), nout = a.lin ? 6 : 4;
+    const int64_t S_in[11] = {n * n * kAB, n * m * kAB, n * n * kQR, m * m * kQR, n * n, n,
+                              n * kQR, m * kQR, n, n * kAB, m * n * kQR};
     const int64_t S_out[6] = {m * n * (N - 1), a.p_all ? n * n * N : n * n, n * N, m * (N - 1),
                               m * (N - 1), a.p_all ? n * N : n};
-    const void *in[10] = {a.A, a.B, a.Q, a.R, a.Qf, a.x0, a.q, a.r, a.qf, a.c};
+    const void *in[11] = {a.A, a.B, a.Q, a.R, a.Qf, a.x0, a.q, a.r, a.qf, a.c, a.M};
     void *out[6] = {a.K, a.P, a.X, a.U, a.d, a.p};
-    size_t off[16], total = 0;
+    size_t off[17], total = 0;
     for (int i = 0; i < nin + nout; ++i) {
         off[i] = total;
         total += ((size_t)(i < nin ? S_in[i] : S_out[i - nin]) * B * es + 255) & ~(size_t)255;
@@ -173,7 +173,7 @@ hipError_t dp_launch_soa_staged(const lqrx::DpArgs &a, hipStream_t s)
     char *base = (char *)blk;
     lqrx::DpArgs a0 = a;
     a0.layout = 0;
-    const void **pin[10] = {&a0.A, &a0.B, &a0.Q, &a0.R, &a0.Qf, &a0.x0, &a0.q, &a0.r, &a0.qf, &a0.c};
+    const void **pin[11] = {&a0.A, &a0.B, &a0.Q, &a0.R, &a0.Qf, &a0.x0, &a0.q, &a0.r, &a0.qf, &a0.c, &a0.M};
     void **pout[6] = {&a0.K, &a0.P, &a0.X, &a0.U, &a0.d, &a0.p};
     for (int i = 0; i < nin && e == hipSuccess; ++i) {        // [S][B] → [B][S]
         *pin[i] = base + off[i];
@@ -248,18 +248,43 @@ int check_affine_ptrs(const void *A, const void *B, const void *c, const void *Q
     return 0;
 }
 
-// lqrx_dp_solve, lqrx_dp_solve_linear (lin != NULL) and lqrx_dp_solve_affine (aff: c and lin,
-// checked by check_affine_ptrs before this); argument numbers in error codes follow the calling
-// entry point's signature
+// Pointer checks of lqrx_dp_solve_cross[_host], in argument order (desc 1, A 2, B 3, c 4, Q 5,
+// R 6, M 7, Qf 8, x0 9, lin 10, K 11 … U 14) — before anything touches the device
+int check_cross_ptrs(const void *A, const void *B, const void *c, const void *Q, const void *R,
+                     const void *M, const void *Qf, const void *x0, const lqrx_dp_linear *lin, void *K,
+                     void *P, void *X, void *U)
+{
+    const void *in[8] = {A, B, c, Q, R, M, Qf, x0};
+    static const char *inm[8] = {"A", "B", "c", "Q", "R", "M", "Qf", "x0"};
+    for (int i = 0; i < 8; ++i)
+        if (!in[i]) return set_err(-(i + 2), "input pointer %d (%s) is NULL", i + 2, inm[i]);
+    if (!lin) return set_err(-10, "lin is NULL (pass zero q, r, qf for a problem without linear cost terms)");
+    const void *lp[5] = {lin->q, lin->r, lin->qf, lin->d, lin->p};
+    static const char *nm[5] = {"q", "r", "qf", "d", "p"};
+    for (int i = 0; i < 5; ++i)
+        if (!lp[i]) return set_err(-10, "lin->%s is NULL", nm[i]);
+    const void *out[4] = {K, P, X, U};
+    for (int i = 0; i < 4; ++i)
+        if (!out[i]) return set_err(-(i + 11), "output pointer %d is NULL", i + 11);
+    return 0;
+}
+
+// lqrx_dp_solve, lqrx_dp_solve_linear (lin != NULL), lqrx_dp_solve_affine (aff: c and lin,
+// checked by check_affine_ptrs before this) and lqrx_dp_solve_cross (cross, with aff: c, M and
+// lin, checked by check_cross_ptrs); argument numbers in error codes follow the calling entry
+// point's signature
 int dp_solve_impl(const lqrx_dp_desc *d, const void *A, const void *B, const void *Q,
                   const void *R, const void *Qf, const void *x0, const lqrx_dp_linear *lin,
                   void *K, void *P, void *X, void *U, int32_t *info, void *stream,
-                  const void *c = nullptr, bool aff = false)
+                  const void *c = nullptr, bool aff = false, const void *M = nullptr,
+                  bool cross = false)
 {
     int st = validate_dp(d);
     if (st) return st;
     if (d->batch == 0) return 0;
-    if (aff) {
+    if (cross) {
+        if ((st = check_cross_ptrs(A, B, c, Q, R, M, Qf, x0, lin, K, P, X, U))) return st;
+    } else if (aff) {
         if ((st = check_affine_ptrs(A, B, c, Q, R, Qf, x0, lin, K, P, X, U))) return st;
     } else {
         const int o = lin ? 1 : 0;   // lqrx_dp_solve_linear: lin is argument 8, outputs shift by one
@@ -285,6 +310,10 @@ int dp_solve_impl(const lqrx_dp_desc *d, const void *A, const void *B, const voi
     if (aff) {
         a.aff = 1;
         a.c = c;
+    }
+    if (cross) {
+        a.cross = 1;
+        a.M = M;
     }
     a.A = A; a.B = B; a.Q = Q; a.R = R; a.Qf = Qf; a.x0 = x0;
     a.K = K; a.P = P; a.X = X; a.U = U; a.info = info;
@@ -318,25 +347,28 @@ int dp_solve_impl(const lqrx_dp_desc *d, const void *A, const void *B, const voi
 int dp_solve_host_impl(const lqrx_dp_desc *d, const void *A, const void *B, const void *Q,
                        const void *R, const void *Qf, const void *x0, const lqrx_dp_linear *lin,
                        void *K, void *P, void *X, void *U, int32_t *info,
-                       const void *c = nullptr, bool aff = false)
+                       const void *c = nullptr, bool aff = false, const void *M = nullptr,
+                       bool cross = false)
 {
     int st = validate_dp(d);
     if (st) return st;
     if (d->batch == 0) return 0;
-    if (aff && (st = check_affine_ptrs(A, B, c, Q, R, Qf, x0, lin, K, P, X, U))) return st;
+    if (cross) {
+        if ((st = check_cross_ptrs(A, B, c, Q, R, M, Qf, x0, lin, K, P, X, U))) return st;
+    } else if (aff && (st = check_affine_ptrs(A, B, c, Q, R, Qf, x0, lin, K, P, X, U))) return st;
     const int o = lin ? 1 : 0;
     const size_t s = dsize(d->dtype), bt = (size_t)d->batch;
     const size_t n = d->n, m = d->m, N = d->N;
     const size_t kAB = d->knot_stride_AB ? N - 1 : 1, kQR = d->knot_stride_QR ? N - 1 : 1;
-    const int nin = aff ? 10 : (lin ? 9 : 6), nout = lin ? 6 : 4;
-    const size_t szin[10] = {n * n * kAB, n * m * kAB, n * n * kQR, m * m * kQR, n * n, n,
-                             n * kQR, m * kQR, n, n * kAB};
-    const void *hin[10] = {A, B, Q, R, Qf, x0, lin ? lin->q : nullptr, lin ? lin->r : nullptr,
-                           lin ? lin->qf : nullptr, c};
+    const int nin = cross ? 11 : (aff ? 10 : (lin ? 9 : 6)), nout = lin ? 6 : 4;
+    const size_t szin[11] = {n * n * kAB, n * m * kAB, n * n * kQR, m * m * kQR, n * n, n,
+                             n * kQR, m * kQR, n, n * kAB, m * n * kQR};
+    const void *hin[11] = {A, B, Q, R, Qf, x0, lin ? lin->q : nullptr, lin ? lin->r : nullptr,
+                           lin ? lin->qf : nullptr, c, M};
     const size_t szout[6] = {m * n * (N - 1), d->p_mode ? n * n * N : n * n, n * N, m * (N - 1),
                              m * (N - 1), d->p_mode ? n * N : n};
     void *hout[6] = {K, P, X, U, lin ? lin->d : nullptr, lin ? lin->p : nullptr};
-    DevBuf din[10], dout[6], dinfo;
+    DevBuf din[11], dout[6], dinfo;
     for (int i = 0; i < nin; ++i) {
         if (!hin[i]) return set_err(i < 6 ? -(i + 2) : -8, "input pointer %s is NULL",
                                     i < 6 ? "" : "in lin");
@@ -356,7 +388,8 @@ int dp_solve_host_impl(const lqrx_dp_desc *d, const void *A, const void *B, cons
     }
     st = dp_solve_impl(d, din[0].p, din[1].p, din[2].p, din[3].p, din[4].p, din[5].p,
                        lin ? &dl : nullptr, dout[0].p, dout[1].p, dout[2].p, dout[3].p,
-                       (int32_t *)dinfo.p, nullptr, aff ? din[9].p : nullptr, aff);
+                       (int32_t *)dinfo.p, nullptr, aff ? din[9].p : nullptr, aff,
+                       cross ? din[10].p : nullptr, cross);
     if (st < 0) return st;
     for (int i = 0; i < nout; ++i) {
         hipError_t e = hipMemcpy(hout[i], dout[i].p, szout[i] * s * bt, hipMemcpyDeviceToHost);
@@ -496,6 +529,23 @@ int lqrx_dp_solve_affine_host(const lqrx_dp_desc *d, const void *A, const void *
                               int32_t *info)
 {
     return dp_solve_host_impl(d, A, B, Q, R, Qf, x0, lin, K, P, X, U, info, c, true);
+}
+
+// cost cross term uᵀMx on top of the affine solve: G = BᵀPA + M_k (see lqrx.h)
+int lqrx_dp_solve_cross(const lqrx_dp_desc *d, const void *A, const void *B, const void *c,
+                        const void *Q, const void *R, const void *M, const void *Qf, const void *x0,
+                        const lqrx_dp_linear *lin, void *K, void *P, void *X, void *U,
+                        int32_t *info, void *stream)
+{
+    return dp_solve_impl(d, A, B, Q, R, Qf, x0, lin, K, P, X, U, info, stream, c, true, M, true);
+}
+
+int lqrx_dp_solve_cross_host(const lqrx_dp_desc *d, const void *A, const void *B, const void *c,
+                             const void *Q, const void *R, const void *M, const void *Qf,
+                             const void *x0, const lqrx_dp_linear *lin, void *K, void *P, void *X,
+                             void *U, int32_t *info)
+{
+    return dp_solve_host_impl(d, A, B, Q, R, Qf, x0, lin, K, P, X, U, info, c, true, M, true);
 }
 
 

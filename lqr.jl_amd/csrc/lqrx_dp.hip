@@ -690,8 +690,16 @@ __device__ __forceinline__ void dp_rollout_full(const DpArgs &a, int64_t b, T *l
 //                into the p image before lin_first() reads it (aff_ptilde() in the kernel: at the
 //                head of lin_first() time-varying, behind the PA product time-invariant); the
 //                rollout adds c_k to x_{k+1}.
+//   VAR_CROSS  : cost cross term uᵀM_k x (lqrx_dp_solve_cross), only with VAR_LIN | VAR_AFF, with
+//                or without VAR_TV: G = BᵀPA + M_k, so the G accumulators start from M_k instead
+//                of zero and every later reader of G (K = XᵀG, Gᵀd, −GᵀK) follows; E, info and
+//                the Newton–Schulz chain do not see M.  M_k (m×n, knot stride with Q, R) is read
+//                from global memory every knot — per knot from HBM when time-varying, the
+//                cache-resident m·n block of the trajectory otherwise (no LDS image: LDS decides
+//                the workgroups per CU on the fp64 2×1 grid and above) — issued
+//                behind the PB / PA products, beside Q, so that it lands under the E product.
 enum : int { VAR_NOSOLVE = 2, VAR_NOROLL = 4, VAR_NOKSTORE = 8, VAR_SWEEPONLY = 16, VAR_TV = 32,
-             VAR_LIN = 64, VAR_AFF = 128 };
+             VAR_LIN = 64, VAR_AFF = 128, VAR_CROSS = 256 };
 
 // Vector products with register tiles (VAR_LIN).  A vector v is read from its LDS image in
 // "row layout" (lane l, slot [i][r] = v[16i + Tile::row(l, r)], the rows a C-layout tile's
@@ -731,6 +739,8 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
     constexpr int MP = C::MP, CS = C::CS;
     constexpr bool TV = (VAR & VAR_TV) != 0, LIN = (VAR & VAR_LIN) != 0, AFF = (VAR & VAR_AFF) != 0;
     static_assert(!AFF || LIN, "VAR_AFF extends VAR_LIN");
+    constexpr bool CROSS = (VAR & VAR_CROSS) != 0;
+    static_assert(!CROSS || (LIN && AFF), "VAR_CROSS extends VAR_LIN | VAR_AFF");
     // Q + AᵀPA in the shadow of the Newton–Schulz chain (PnShadow): time-invariant A only
     constexpr bool SHADOW = !TV && (VAR & (VAR_NOSOLVE | VAR_SWEEPONLY)) == 0;
     constexpr int NP = C::NP;
@@ -759,6 +769,9 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
     const T *Ab = (const T *)a.A + b * nn * kAB, *Bb = (const T *)a.B + b * nm * kAB;
     const T *Qb = (const T *)a.Q + b * nn * kQR, *Rb = (const T *)a.R + b * mm * kQR;
     const T *Qg = Qb;
+    // cross term M_k (m×n): knot stride with Q, R
+    const size_t sM = (CROSS && kQR > 1) ? nm : 0;
+    const T *Mb = CROSS ? (const T *)a.M + b * nm * kQR : nullptr;
 
     acc At[NT][NT], Bt[NT][MT], Rt[MT][MT], P[NT][NT];
     const size_t k0 = TV ? (size_t)(N - 2) : 0;                 // first backward knot k = N-1
@@ -897,6 +910,17 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
         tiles_zero<T, NT, NT>(PA);
         mma_tn<T, NT, NT, NT>(PA, P, At);                          // :40 PA = P A
         if constexpr (AFF && !TV) aff_ptilde();
+        // VAR_CROSS: G starts from M_k (zero padded past m, n).  The loads are issued here, beside
+        // Q's, and land behind the E product; issued ahead of PB / PA they held G's registers across
+        // both products, which spilled 11 VGPRs on the fp64 2×1 grid at 2 waves/SIMD and cost the
+        // fp32 2×1 grid a wave per SIMD.  The lane index is laundered so that the per-lane offsets
+        // are re-derived every knot: a time-invariant M has loop-invariant addresses, and kept live
+        // across the knot loop they cost the same two grids 2 spilled VGPRs / the wave
+        if constexpr (CROSS) {
+            int lm = lane;
+            asm volatile("" : "+v"(lm));
+            tiles_load<T, MT, NT, FULL>(G, Mb + (size_t)(k - 1) * sM, m, n, m, lm, false);
+        }
         if constexpr (TV) {
             tiles_load_lower<T, NT, FULL>(Pn, Qb + (size_t)(k - 1) * sQ, n, n, lane);
         }
@@ -906,8 +930,8 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
 #pragma unroll
             for (int j = 0; j < MT; ++j) E[i][j] = Rt[i][j];
         mma_tn<T, NT, MT, MT>(E, Bt, PB);                          // :39 E = R + B'PB
-        tiles_zero<T, MT, NT>(G);
-        mma_tn<T, NT, MT, NT>(G, Bt, PA);                          // :41 K = B'PA
+        if constexpr (!CROSS) tiles_zero<T, MT, NT>(G);
+        mma_tn<T, NT, MT, NT>(G, Bt, PA);                          // :41 K = B'PA (+ M_k)
         // :51 Q + A'PA (lower): independent of the solve.  Time-invariant A: issued in chunks in
         // the shadow of the Newton–Schulz chain below (PnShadow); time-varying: here, before
         // A_k leaves the tiles.
@@ -1687,7 +1711,7 @@ template <typename T, int NT, int MT, int WAVES, int VAR>
 static hipError_t launch_dp(const DpArgs &a, hipStream_t s);
 
 // One tile grid's variants, each at its launch bound (waves per SIMD) — the occupancy table:
-//   grid (16·NT × 16·MT)   plain / LIN / AFF   VAR_TV   VAR_TV|VAR_LIN(|VAR_AFF)
+//   grid (16·NT × 16·MT)   plain / LIN / AFF / CROSS   VAR_TV   VAR_TV|VAR_LIN(|VAR_AFF(|VAR_CROSS))
 //   1×1                     2                   2        2
 //   2×1                     2                   2        fp64 1, fp32 2
 //   2×2                     2                   1        1
@@ -1710,6 +1734,9 @@ static hipError_t launch_dp_tv(const DpArgs &a, hipStream_t s)
     // 1×1 (double) and up to 2×1 (float) grids; time-invariant LIN keeps the plain kernel's
     // occupancy (its vector work sits after the solve, where fewer tiles are live)
     constexpr int LW = (NT * MT <= (sizeof(T) == 4 ? 2 : 1)) ? 2 : 1;
+    // cost cross term (needs lin and aff): the launch bounds of the affine variants
+    if (a.cross && (a.tv_AB || a.tv_QR)) return launch_dp<T, NT, MT, LW, VAR_TV | VAR_LIN | VAR_AFF | VAR_CROSS>(a, s);
+    if (a.cross) return launch_dp<T, NT, MT, WAVES, VAR_LIN | VAR_AFF | VAR_CROSS>(a, s);
     // affine offset (needs lin): the launch bounds of the linear-terms variants
     if (a.aff && (a.tv_AB || a.tv_QR)) return launch_dp<T, NT, MT, LW, VAR_TV | VAR_LIN | VAR_AFF>(a, s);
     if (a.aff) return launch_dp<T, NT, MT, WAVES, VAR_LIN | VAR_AFF>(a, s);
@@ -1751,7 +1778,7 @@ hipError_t dp_launch(const DpArgs &a_in, hipStream_t s)
         // or without linear terms (LQRX_DP_WG4=0 in the environment: the one-wave kernel, for A/B
         // runs and tests)
         static const bool wg4 = [] { const char *e = std::getenv("LQRX_DP_WG4"); return !(e && *e == '0'); }();
-        // (an affine call takes the one-wave kernel below: dp_wg4_kernel has no c_k)
+        // (an affine or cross call takes the one-wave kernel below: dp_wg4_kernel has no c_k, no M_k)
         if (wg4 && !a.aff && a.n == 64 && (a.m == 16 || a.m == 32))
             return a.m == 16 ? launch_wg4<1>(a, s) : launch_wg4<2>(a, s);
         if (nt <= 4 && mt <= 2) return launch_dp_tv<double, 4, 2>(a, s);

@@ -13,7 +13,10 @@
 // on the VALU.
 // Time-varying knot strides, all-P output, linear cost terms (d, p) as in the other kernels; the
 // affine offset c_k of lqrx_dp_solve_affine (a.aff, with a.lin): p ← p + P c_k at the head of the
-// knot, before w = r + Bᵀp, and x_{k+1} += c_k in the rollout.
+// knot, before w = r + Bᵀp, and x_{k+1} += c_k in the rollout; the cost cross term M_k of
+// lqrx_dp_solve_cross (a.cross, with a.lin and a.aff): K ← BᵀPA starts from M_k (wg_mm's C
+// argument, as E starts from R) and Mᵀ_k is added into APB, so that APB·K and APB·d are Gᵀ· with
+// G = BᵀPA + M_k.
 #include "lqrx_internal.h"
 #include "lqrx_tile.h"
 #include "lqrx_wg.h"
@@ -46,6 +49,9 @@ __global__ __launch_bounds__(BT) void dp_big_kernel(const DpArgs a, T *__restric
     const bool aff = lin && a.aff != 0;
     const size_t sc = a.tv_AB ? (size_t)n : 0;
     const T *c0 = aff ? (const T *)a.c + b * n * kAB : nullptr;
+    const bool cross = aff && a.cross != 0;
+    const size_t sM = a.tv_QR ? nm : 0;
+    const T *M0 = cross ? (const T *)a.M + b * nm * kQR : nullptr;
 
     T *w0 = ws + (size_t)blockIdx.x * ws_elems;
     T *P = w0, *Pn = P + nn, *PA = Pn + nn, *PB = PA + nn, *APB = PB + nm, *E = APB + nm;
@@ -105,9 +111,14 @@ __global__ __launch_bounds__(BT) void dp_big_kernel(const DpArgs a, T *__restric
         // :39 E = R + B'PB ; :41 K = B'PA ; :50 APB = A'PB
         const Mat<T> PBm{PB, 1, (size_t)n}, PAm{PA, 1, (size_t)n};
         wg::wg_mm<T, 1, 1>(E, m, m, m, R, Bm, PBm, n, none, none, 0, tid);
-        wg::wg_mm<T, 1, 1>(K, m, m, n, nullptr, Bm, PAm, n, none, none, 0, tid);
+        const T *Mk = cross ? M0 + (size_t)(k - 1) * sM : nullptr;   // K = M_k + B'PA
+        wg::wg_mm<T, 1, 1>(K, m, m, n, Mk, Bm, PAm, n, none, none, 0, tid);
         wg::wg_mm<T, 1, 1>(APB, n, n, m, nullptr, Am, PBm, n, none, none, 0, tid);
         __syncthreads();
+        // APB += M_kᵀ (= Gᵀ): its readers (:51, p_) come after the factor and the solves, which
+        // synchronise on exit
+        if (cross)
+            for (size_t e = tid; e < nm; e += BT) APB[e] += Mk[(e / n) + (e % n) * (size_t)m];
         // :29 potrf!('U', E) — blocked left-looking (lqrx_wg.h); a failed pivot stops the factor
         // (as LAPACK) and reports this knot
         const int f = wg::wg_potrf<T>(E, m, m, tid);

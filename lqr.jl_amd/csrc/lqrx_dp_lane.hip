@@ -55,7 +55,9 @@ __device__ __forceinline__ void lane_load(T (&D)[RP][CP], const T *__restrict__ 
 // AFF (affine dynamics x⁺ = Ax + Bu + c, lqrx_dp_solve_affine; needs LIN; c follows A, B: per
 // knot with TV and tv_AB): p̃ = p + P c_k replaces p in both uses above (formed in registers
 // from the lower triangle of P_{k+1}), and the rollout adds c_k to x_{k+1}.
-template <typename T, int NP, int MP, bool TV, bool SOA, bool LIN = false, bool AFF = false>
+// CROSS (cost cross term uᵀM_k x, lqrx_dp_solve_cross; needs LIN and AFF; M follows Q, R: per
+// knot with TV and tv_QR, prefetched with them): G = BᵀPA + M_k — G[c][j] starts from M[c][j].
+template <typename T, int NP, int MP, bool TV, bool SOA, bool LIN = false, bool AFF = false, bool CROSS = false>
 __global__ __launch_bounds__(64) void dp_lane_kernel(const DpArgs a)
 {
     const int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x;
@@ -115,6 +117,12 @@ __global__ __launch_bounds__(64) void dp_lane_kernel(const DpArgs a)
 #pragma unroll
         for (int i = 0; i < NP; ++i) cv[i] = i < n ? cb[i * es] : (T)0;
     }
+    static_assert(!CROSS || (LIN && AFF), "CROSS extends LIN && AFF");
+    constexpr int XM = CROSS ? MP : 1, XN = CROSS ? NP : 1;
+    const int64_t sM = a.tv_QR ? nm : 0;
+    const T *Mb = CROSS ? (const T *)a.M + tb(nm * kQR) : nullptr;
+    T Mx[XM][XN];
+    if constexpr (CROSS && !TV) lane_load<T, MP, NP>(Mx, Mb, m, n, (T)0, es);   // time-invariant M: loaded once
     if constexpr (LIN) {
         const T *qf = (const T *)a.qf + tb(n);
 #pragma unroll
@@ -134,8 +142,10 @@ __global__ __launch_bounds__(64) void dp_lane_kernel(const DpArgs a)
     // time-varying: knot k's matrices are prefetched during knot k+1
     constexpr int TN = TV ? NP : 1, TM = TV ? MP : 1;
     T An[TN][TN], Bn[TN][TM], Qn[TN][TN], Rn[TM][TM];
+    T Mn[CROSS && TV ? MP : 1][CROSS && TV ? NP : 1];
     auto fetch_tv = [&](int k) {
         if (k < 1) return;
+        if constexpr (CROSS && TV) lane_load<T, MP, NP>(Mn,Mb + (int64_t)(k - 1) * sM * es, m, n, (T)0, es);
         if constexpr (LIN) {
 #pragma unroll
             for (int i = 0; i < NP; ++i) qn[i] = i < n ? qb[((int64_t)(k - 1) * sq + i) * es] : (T)0;
@@ -187,6 +197,12 @@ __global__ __launch_bounds__(64) void dp_lane_kernel(const DpArgs a)
 #pragma unroll
             for (int i = 0; i < NP; ++i) cv[i] = cn[i];
         }
+        if constexpr (CROSS && TV) {
+#pragma unroll
+            for (int i = 0; i < MP; ++i)
+#pragma unroll
+                for (int j = 0; j < NP; ++j) Mx[i][j] = Mn[i][j];
+        }
         if constexpr (TV) fetch_tv(k - 1);
         // P is symmetric: only P[i][j], i ≥ j, is maintained
 #define PS(i, j) ((i) >= (j) ? P[i][j] : P[j][i])
@@ -229,8 +245,9 @@ __global__ __launch_bounds__(64) void dp_lane_kernel(const DpArgs a)
                 E[c][d] = s;
             }
 #pragma unroll
-            for (int j = 0; j < NP; ++j) {                       // :41 G = BᵀPA
+            for (int j = 0; j < NP; ++j) {                       // :41 G = BᵀPA (+ M_k)
                 T s = (T)0;
+                if constexpr (CROSS) s = Mx[c][j];
 #pragma unroll
                 for (int i = 0; i < NP; ++i) s = fma(B[i][c], PA[i][j], s);
                 G[c][j] = s;
@@ -1054,7 +1071,12 @@ static hipError_t launch_lane(const DpArgs &a, hipStream_t s)
 {
     dim3 grid((unsigned)((a.batch + 63) / 64)), block(64);
     const bool tv = a.tv_AB || a.tv_QR, soa = a.layout == 1;
-    if (a.aff && tv && soa) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, true, true, true, true>), grid, block, 0, s, a);
+    if (a.cross && !(a.lin && a.aff)) return hipErrorInvalidValue;   // the cross term extends the affine solve
+    if (a.cross && tv && soa) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, true, true, true, true, true>), grid, block, 0, s, a);
+    else if (a.cross && tv) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, true, false, true, true, true>), grid, block, 0, s, a);
+    else if (a.cross && soa) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, false, true, true, true, true>), grid, block, 0, s, a);
+    else if (a.cross) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, false, false, true, true, true>), grid, block, 0, s, a);
+    else if (a.aff && tv && soa) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, true, true, true, true>), grid, block, 0, s, a);
     else if (a.aff && tv) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, true, false, true, true>), grid, block, 0, s, a);
     else if (a.aff && soa) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, false, true, true, true>), grid, block, 0, s, a);
     else if (a.aff) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, false, false, true, true>), grid, block, 0, s, a);

@@ -32,6 +32,11 @@ struct DpArgs {
     // that every earlier field keeps its kernel-argument offset.)
     int aff;
     const void *c;
+    // cost cross term uᵀMx (lqrx_dp_solve_cross; needs lin = 1 and aff = 1): M is m×n column-major,
+    // per knot with tv_QR (knot stride m·n, knot k at k−1, like Q and R), m·n per trajectory
+    // otherwise.  G = BᵀPA + M_k.  (Appended: every earlier field keeps its offset.)
+    int cross;
+    const void *M;
 };
 
 hipError_t dp_launch(const DpArgs &a, hipStream_t s);

@@ -94,6 +94,10 @@ _SIGS = {
                              + [_VP] * 4 + [_VP, _VP]),
     "lqrx_dp_solve_affine_host": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 7
                                   + [C.POINTER(DpLinear)] + [_VP] * 5),
+    "lqrx_dp_solve_cross": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 8 + [C.POINTER(DpLinear)]
+                            + [_VP] * 4 + [_VP, _VP]),
+    "lqrx_dp_solve_cross_host": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 8
+                                 + [C.POINTER(DpLinear)] + [_VP] * 5),
     "lqrx_dp_solve_host_devices": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 10 + [_VP, _VP, C.c_int32]),
     "lqrx_dp_solve_linear_host_devices": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 6 + [C.POINTER(DpLinear)]
                                           + [_VP] * 5 + [_VP, C.c_int32]),

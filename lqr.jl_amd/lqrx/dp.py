@@ -9,7 +9,8 @@ Reference surface (Julia, /root/reference/src):
   compute_gain!(K, solver, prob), compute_ctg!(K, solver, prob)      :34-52 (per knot)
 Extension (no upstream counterpart): linear cost terms q, r, qf on
 LQRProblem / LQRBatch → feedforward d and linear cost-to-go p (lqrx_dp_solve_linear); an
-affine dynamics offset c, x⁺ = A x + B u + c (lqrx_dp_solve_affine), which also returns d, p.
+affine dynamics offset c, x⁺ = A x + B u + c (lqrx_dp_solve_affine), which also returns d, p; a
+cost cross term uᵀM x (lqrx_dp_solve_cross), G = BᵀPA + M, on top of both.
 
 Array conventions here: a single problem uses plain (rows, cols) numpy matrices; batches
 use numpy arrays shaped (batch, rows, cols).  The C ABI wants Julia column-major with the
@@ -77,6 +78,9 @@ class LQRProblem:
     # affine dynamics offset (extension): x_{k+1} = A x_k + B u_k + c; c (n,) or, together with a
     # knot axis on A and B, (N-1, n)
     c: np.ndarray | None = None
+    # cost cross term (extension): stage cost + uᵀM x; M (m, n) or, together with a knot axis on
+    # Q and R, (N-1, m, n)
+    M: np.ndarray | None = None
 
     def size(self):
         n, m = self.B.shape[-2:]
@@ -106,7 +110,7 @@ class LQRSolution:
     @classmethod
     def of(cls, prob: LQRProblem, all_P: bool = False):
         n, m, N = prob.size()
-        lin = prob.q is not None or prob.c is not None
+        lin = prob.q is not None or prob.c is not None or prob.M is not None
         return cls(np.zeros((N - 1, m, n)), np.zeros((N, n)), np.zeros((N - 1, m)),
                    np.zeros((N, n, n)) if all_P else np.zeros((n, n)),
                    d=np.zeros((N - 1, m)) if lin else None,
@@ -150,6 +154,7 @@ class LQRBatch:
     r: np.ndarray | None = None    # (batch, m) or (batch, N-1, m)
     qf: np.ndarray | None = None   # (batch, n)
     c: np.ndarray | None = None    # (batch, n) or (batch, N-1, n) — affine offset x⁺ = Ax + Bu + c
+    M: np.ndarray | None = None    # (batch, m, n) or (batch, N-1, m, n) — cost cross term uᵀM x
 
     @property
     def batch(self):
@@ -177,9 +182,15 @@ class LQRBatch:
             for p in probs:   # a knot axis on c needs one on A and B, and vice versa
                 if (np.ndim(p.c) == 2) != (np.ndim(p.A) == 3):
                     raise ValueError("c carries a knot axis (N-1, n) exactly when A and B carry one")
+        cross = probs[0].M is not None
+        if cross:
+            for p in probs:   # M is a cost term: its knot axis goes with the one on Q and R
+                if (np.ndim(p.M) == 3) != (np.ndim(p.Q) == 3):
+                    raise ValueError("M carries a knot axis (N-1, m, n) exactly when Q and R carry one")
         return cls(st("A"), st("B"), st("Q"), st("R"), st("Qf"), st("x0"), probs[0].N,
                    q=st("q") if lin else None, r=st("r") if lin else None,
-                   qf=st("qf") if lin else None, c=st("c") if aff else None)
+                   qf=st("qf") if lin else None, c=st("c") if aff else None,
+                   M=st("M") if cross else None)
 
 
 def _ptr(a: np.ndarray):
@@ -201,12 +212,24 @@ def solve_batch(b: LQRBatch, dtype: int = _lib.F64, all_P: bool = False, layout:
     result is the same logical arrays).  devices = [d0, d1, …] shards the batch over those
     GPUs in one call (lqrx_dp_solve[_linear]_host_devices; repeats allowed).  With b.c (affine
     dynamics) the call is lqrx_dp_solve_affine_host: missing q, r, qf are zeros, d and p are
-    returned; it has no devices= form."""
+    returned; it has no devices= form.  With b.M (cost cross term) the call is
+    lqrx_dp_solve_cross_host: a missing c is zeros as well; no devices= form either."""
     n, m, N = b.size()
     bt = b.batch
     tvAB, tvQR = b.time_varying()
     npdt = np.float64 if dtype == _lib.F64 else np.float32
-    aff = b.c is not None
+    cross = b.M is not None
+    aff = b.c is not None or cross
+    if cross:
+        if devices is not None:
+            raise ValueError("devices= is not available with a cost cross term M")
+        if np.shape(b.M)[-2:] != (m, n):
+            raise ValueError("M is (m, n) per trajectory (per knot), the shape of K")
+        if (np.ndim(b.M) == 4) != bool(tvQR):
+            raise ValueError("M carries a knot axis (batch, N-1, m, n) exactly when Q and R carry one")
+        if b.c is None:
+            b = LQRBatch(b.A, b.B, b.Q, b.R, b.Qf, b.x0, b.N, b.extra, q=b.q, r=b.r, qf=b.qf,
+                         c=np.zeros((bt, N - 1, n) if tvAB else (bt, n), npdt), M=b.M)
     if aff:
         if devices is not None:
             raise ValueError("devices= is not available with an affine offset c")
@@ -217,7 +240,7 @@ def solve_batch(b: LQRBatch, dtype: int = _lib.F64, all_P: bool = False, layout:
         b = LQRBatch(b.A, b.B, b.Q, b.R, b.Qf, b.x0, b.N, b.extra,
                      q=b.q if b.q is not None else (zeros(bt, kq, n) if tvQR else zeros(bt, n)),
                      r=b.r if b.r is not None else (zeros(bt, kq, m) if tvQR else zeros(bt, m)),
-                     qf=b.qf if b.qf is not None else zeros(bt, n), c=b.c)
+                     qf=b.qf if b.qf is not None else zeros(bt, n), c=b.c, M=b.M)
     lib = _lib.load()
     ins = [to_abi(np.asarray(x, dtype=npdt)) for x in (b.A, b.B, b.Q, b.R, b.Qf)]
     x0 = np.ascontiguousarray(np.asarray(b.x0, dtype=npdt))
@@ -250,7 +273,14 @@ def solve_batch(b: LQRBatch, dtype: int = _lib.F64, all_P: bool = False, layout:
             cv = np.ascontiguousarray(np.asarray(b.c, dtype=npdt).reshape(bt * (N - 1 if tvAB else 1) * n))
             if layout == 1:
                 cv = to_soa(cv, bt)
-            rc = _lib.check(lib.lqrx_dp_solve_affine_host(*args[:3], _ptr(cv), *args[3:]))
+            if cross:   # M follows Q and R: argument 7
+                Mv = to_abi(np.asarray(b.M, dtype=npdt)).reshape(-1)
+                if layout == 1:
+                    Mv = to_soa(Mv, bt)
+                rc = _lib.check(lib.lqrx_dp_solve_cross_host(*args[:3], _ptr(cv), *args[3:5], _ptr(Mv),
+                                                             *args[5:]))
+            else:
+                rc = _lib.check(lib.lqrx_dp_solve_affine_host(*args[:3], _ptr(cv), *args[3:]))
         elif devices is None:
             rc = _lib.check(lib.lqrx_dp_solve_linear_host(*args))
         else:
@@ -286,7 +316,7 @@ def solve(sol: LQRSolution, solver: DPSolver, prob: LQRProblem) -> LQRSolution:
     sol.U[...] = out["U"][0]
     sol.P[...] = out["P"][0]
     sol.info = int(out["info"][0])
-    if prob.q is not None or prob.c is not None:
+    if prob.q is not None or prob.c is not None or prob.M is not None:
         sol.d = out["d"][0]
         sol.p = out["p"][0]
     return sol
@@ -369,7 +399,8 @@ def dp_solve_device(t: dict, N: int, p_mode: int = 0, stream: int | None = None,
 
     t: dict with torch tensors A, B, Q, R, Qf, x0 on the GPU and ints n, m, batch; with
     tensors q, r, qf as well it runs lqrx_dp_solve_linear and also returns d and p; with a
-    tensor c too (n·batch, or n·(N−1)·batch with tv_AB) it runs lqrx_dp_solve_affine.
+    tensor c too (n·batch, or n·(N−1)·batch with tv_AB) it runs lqrx_dp_solve_affine; with a
+    tensor M on top of those (m·n·batch, or m·n·(N−1)·batch with tv_QR) lqrx_dp_solve_cross.
     Returns dict of output tensors (K, P, X, U, info[, d, p]).  `stream` is a raw hipStream_t
     (torch.cuda.current_stream().cuda_stream); None = the null stream, synchronous.
     """
@@ -391,13 +422,20 @@ def dp_solve_device(t: dict, N: int, p_mode: int = 0, stream: int | None = None,
     st = C.c_void_p(stream) if stream else None
     if t.get("c") is not None and t.get("q") is None:
         raise ValueError("dp_solve_device: c needs q, r, qf (zeros for a problem without cost terms)")
+    if t.get("M") is not None and t.get("c") is None:
+        raise ValueError("dp_solve_device: M needs c and q, r, qf (zeros where the problem has none)")
     if t.get("q") is not None:
         if "d" not in out:
             out["d"] = torch.empty(bt * (N - 1) * m, dtype=tdt, device=dev)
             out["p"] = torch.empty(bt * n * (N if p_mode else 1), dtype=tdt, device=dev)
         ln = _lib.DpLinear(t["q"].data_ptr(), t["r"].data_ptr(), t["qf"].data_ptr(),
                            out["d"].data_ptr(), out["p"].data_ptr())
-        if t.get("c") is not None:
+        if t.get("M") is not None:
+            rc = lib.lqrx_dp_solve_cross(C.byref(d), p(t["A"]), p(t["B"]), p(t["c"]), p(t["Q"]),
+                                         p(t["R"]), p(t["M"]), p(t["Qf"]), p(t["x0"]), C.byref(ln),
+                                         p(out["K"]), p(out["P"]), p(out["X"]), p(out["U"]),
+                                         p(out["info"]), st)
+        elif t.get("c") is not None:
             rc = lib.lqrx_dp_solve_affine(C.byref(d), p(t["A"]), p(t["B"]), p(t["c"]), p(t["Q"]),
                                           p(t["R"]), p(t["Qf"]), p(t["x0"]), C.byref(ln), p(out["K"]),
                                           p(out["P"]), p(out["X"]), p(out["U"]), p(out["info"]), st)

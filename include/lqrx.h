@@ -46,9 +46,10 @@ extern "C" {
                                    KKT layout 1 for every structure (staged);
                                    lqrx_dp_compute_ctg[_host] (per-knot surface);
                                 5: lqrx_*_host_devices (one call sharded over GPUs);
-                                   lqrx_dp_solve_affine[_host] and lqrx_dp_solve_cross[_host]
-                                   are additive to ABI 5 (no existing signature or struct
-                                   changed, the number stays 5): detect them by symbol (dlsym) */
+                                   lqrx_dp_solve_affine[_host], lqrx_dp_solve_cross[_host] and
+                                   lqrx_dp_solve_value[_host] are additive to ABI 5 (no existing
+                                   signature or struct changed, the number stays 5): detect
+                                   them by symbol (dlsym) */
 
 #define LQRX_F64 0
 #define LQRX_F32 1
@@ -226,7 +227,8 @@ int lqrx_dp_solve_affine_host(const lqrx_dp_desc *desc, const void *A, const voi
  * with its kernel routing: n ≤ 4 the lane-per-trajectory kernel, fp64 n = 64 the one-wave
  * register-tiled kernel, past the register tiles the workgroup-per-trajectory kernel.
  * Out of scope: there is no _host_devices twin, no lqrx_dp_compute_ctg with a cross term, and
- * the constant of the value function is not formed.  Additive to ABI 5: detect by symbol.
+ * the constant of the value function is not formed (lqrx_dp_solve_value below forms it).
+ * Additive to ABI 5: detect by symbol.
  * ------------------------------------------------------------------------------------ */
 int lqrx_dp_solve_cross(const lqrx_dp_desc *desc, const void *A, const void *B, const void *c,
                         const void *Q, const void *R, const void *M, const void *Qf,
@@ -238,6 +240,53 @@ int lqrx_dp_solve_cross_host(const lqrx_dp_desc *desc, const void *A, const void
                              const void *c, const void *Q, const void *R, const void *M,
                              const void *Qf, const void *x0, const lqrx_dp_linear *lin, void *K,
                              void *P, void *X, void *U, int32_t *info);
+
+/* ------------------------------------------------------------------------------------
+ * DP path with the value function's constant: the solve of lqrx_dp_solve_cross, which also
+ * returns the third part of V_k(x) = ½xᵀP_k x + p_kᵀx + s_k and the two numbers a caller wants
+ * right after a backward pass — the optimal cost (ranking a sampling / multi-start MPC batch,
+ * logging) and the expected reduction of an iLQR / DDP line search.  With the names of the
+ * cross recursion above (E = R_k + BᵀPB, p̃ = p_{k+1} + P_{k+1}c_k, h = r_k + Bᵀp̃, d_k = E⁻¹h):
+ *   s_N = 0
+ *   s_k = s_{k+1} + c_kᵀ(p_{k+1} + ½P_{k+1}c_k) − ½h_kᵀd_k
+ *   dV  = Σ_{k=1}^{N−1} h_kᵀd_k               (≥ 0 when every E is positive definite;
+ *                                              ΔV(α) = −α(1 − α/2)·dV is the Armijo reference)
+ *   J   = ½x0ᵀP_1x0 + p_1ᵀx0 + s_1            (= the cost of the X, U the solve returns)
+ * With c = 0, s_1 = −½dV.  K, P, d, p, X, U and info are exactly those of lqrx_dp_solve_cross
+ * on the same data.  Arguments, layouts, knot strides and kernel routing are those of
+ * lqrx_dp_solve_cross, plus val behind lin:
+ *   val->s   required.  p_mode 0: batch elements, s_1 per trajectory.  p_mode 1: N·batch, s_k of
+ *            trajectory b at [b·N + (k−1)] (layout 0) or [(k−1)·batch + b] (layout 1), s_N = 0.
+ *   val->dV  optional (NULL: not written): batch elements.
+ *   val->J   optional (NULL: not formed): batch elements, accumulated in double from P_1, p_1,
+ *            s_1 and x0 by one small kernel behind the solve, on the same stream.
+ * dV, J and the p_mode-0 s are batch vectors in both layouts.  The element type is desc.dtype.
+ * For a trajectory with info ≠ 0 the three values are unspecified; every other trajectory is
+ * unaffected.  s_1 is the same bits in both p_modes.
+ * Error codes follow the argument position: desc −1, A −2, B −3, c −4, Q −5, R −6, M −7,
+ * Qf −8, x0 −9, lin or one of its members −10, val or its member s −11, K −12, P −13, X −14,
+ * U −15, decided before the device is touched; batch = 0 returns 0.
+ * Out of scope: there is no _host_devices twin, no per-knot lqrx_dp_compute_ctg form, and no
+ * variant without the linear, affine and cross work (a caller without c, M, q, r passes zeros
+ * and pays for them).  Additive to ABI 5: detect by symbol.
+ * ------------------------------------------------------------------------------------ */
+typedef struct lqrx_dp_value {
+    void *s;    /* out, required: batch (p_mode 0: s_1) or N·batch (p_mode 1: s_k, s_N = 0) */
+    void *dV;   /* out, optional (NULL): batch, Σ_k h_kᵀd_k                               */
+    void *J;    /* out, optional (NULL): batch, V_1(x0)                                   */
+} lqrx_dp_value;
+
+int lqrx_dp_solve_value(const lqrx_dp_desc *desc, const void *A, const void *B, const void *c,
+                        const void *Q, const void *R, const void *M, const void *Qf,
+                        const void *x0, const lqrx_dp_linear *lin, const lqrx_dp_value *val,
+                        void *K, void *P, void *X, void *U, int32_t *info, void *stream);
+
+/* host pointers in lin, val and everywhere else: H2D, solve, D2H, synchronous */
+int lqrx_dp_solve_value_host(const lqrx_dp_desc *desc, const void *A, const void *B,
+                             const void *c, const void *Q, const void *R, const void *M,
+                             const void *Qf, const void *x0, const lqrx_dp_linear *lin,
+                             const lqrx_dp_value *val, void *K, void *P, void *X, void *U,
+                             int32_t *info);
 
 /* ------------------------------------------------------------------------------------
  * KKT path: one inner solve of CholeskySolver._solve!(solver)

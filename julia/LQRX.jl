@@ -204,6 +204,10 @@ struct DpLinear
     q::Ptr{Cvoid}; r::Ptr{Cvoid}; qf::Ptr{Cvoid}
     d::Ptr{Cvoid}; p::Ptr{Cvoid}
 end
+# value-function constant (lqrx_dp_value): s required, dV and J optional (C_NULL), all outputs
+struct DpValue
+    s::Ptr{Cvoid}; dV::Ptr{Cvoid}; J::Ptr{Cvoid}
+end
 
 """
     solve_linear!(sol, d, p, solver, prob, q, r, qf)
@@ -231,7 +235,7 @@ function solve_linear!(sol::LQRSolution{T}, d::Array{T,3}, p::Array{T}, solver::
 end
 
 """
-    solve_linear!(sol, d, p, solver, prob, q, r, qf, c; M = nothing)
+    solve_linear!(sol, d, p, solver, prob, q, r, qf, c; M = nothing, value = false)
 
 The same solve with affine dynamics x_{k+1} = A x_k + B u_k + c (c: n×batch, the constant
 term of a linearisation about a trajectory that is not an equilibrium); q, r, qf may be
@@ -240,16 +244,38 @@ zeros.  lqrx_dp_solve_affine_host (c is argument 4, after A and B).
 With the keyword `M` (m×n×batch, one column-major m×n block per trajectory) the stage cost gains
 the cross term uᵀM x, G = BᵀPA + M: lqrx_dp_solve_cross_host (M is argument 7, after Q and R);
 c may be zeros.  Both entries are additive to ABI 5 and are bound by symbol.
+
+With `value = true` the call is lqrx_dp_solve_value_host (val is argument 11, after lin; a missing
+`M` is passed as zeros) and the return value is `(s = …, dV = …, J = …)`: the value function's
+constant (s₁ per trajectory, or N×batch with every s_k, s_N = 0, when `sol.P` holds every P_k),
+the expected reduction Σ_k h_kᵀd_k and the optimal cost V₁(x0), one per trajectory.  Also additive
+to ABI 5.
 """
 function solve_linear!(sol::LQRSolution{T}, d::Array{T,3}, p::Array{T}, solver::DPSolver{T},
                        prob::LQRBatch{T}, q::Matrix{T}, r::Matrix{T}, qf::Matrix{T},
-                       c::Matrix{T}; M::Union{Nothing,Array{T,3}} = nothing) where T
+                       c::Matrix{T}; M::Union{Nothing,Array{T,3}} = nothing, value::Bool = false) where T
     n, m, N = solver.n, solver.m, solver.N
     batch = size(prob.A, 3)
     size(c) == (n, batch) || throw(ArgumentError("c must be n×batch"))
     M === nothing || size(M) == (m, n, batch) || throw(ArgumentError("M must be m×n×batch"))
     all_P = ndims(sol.P) == 4
     desc = Ref(DpDesc(n, m, N, dtypecode(T), batch, 0, all_P ? 1 : 0, 0, 0))
+    if value
+        Mv = M === nothing ? zeros(T, m, n, batch) : M
+        s = all_P ? Matrix{T}(undef, N, batch) : Vector{T}(undef, batch)
+        dV, J = Vector{T}(undef, batch), Vector{T}(undef, batch)
+        GC.@preserve prob sol d p q r qf c Mv s dV J begin
+            lin = Ref(DpLinear(pointer(q), pointer(r), pointer(qf), pointer(d), pointer(p)))
+            val = Ref(DpValue(pointer(s), pointer(dV), pointer(J)))
+            rc = ccall((:lqrx_dp_solve_value_host, liblqrx), Cint,
+                       (Ref{DpDesc}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T},
+                        Ref{DpLinear}, Ref{DpValue}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{Int32}),
+                       desc, prob.A, prob.B, c, prob.Q, prob.R, Mv, prob.Qf, prob.x0, lin, val,
+                       sol.Kdata, sol.P, sol.Xdata, sol.Udata, sol.info)
+        end
+        check(rc)
+        return (s = s, dV = dV, J = J)
+    end
     GC.@preserve prob sol d p q r qf c M begin
         lin = Ref(DpLinear(pointer(q), pointer(r), pointer(qf), pointer(d), pointer(p)))
         if M === nothing

@@ -150,19 +150,23 @@ namespace {
 // outputs transposed back into the caller's SoA buffers.  Extra HBM traffic: one read + one
 // write of every input and output (2× the algorithmic bytes); the n ≤ 4 kernels read SoA
 // natively instead.
-hipError_t dp_launch_soa_staged(const lqrx::DpArgs &a, hipStream_t s)
+// A value solve (a.value) stages s as a seventh output when it holds every s_k (p_all); the batch
+// vectors s_1, dV and J are the same in both layouts and are written in place.  J is formed on the
+// layout-0 scratch, before the transposition back.
+hipError_t dp_launch_soa_staged(const lqrx::DpArgs &a, hipStream_t s, void *J = nullptr)
 {
     const int64_t B = a.batch, n = a.n, m = a.m, N = a.N, es = dsize(a.dtype);
     const int64_t kAB = a.tv_AB ? N - 1 : 1, kQR = a.tv_QR ? N - 1 : 1;
     // inputs A B Q R Qf x0 [q r qf [c [M]]], outputs K P X U [d p]
-    const int nin = a.cross ? 11 : (a.aff ? 10 : (a.lin ? 9 : 6)), nout = a.lin ? 6 : 4;
+    const int nin = a.cross ? 11 : (a.aff ? 10 : (a.lin ? 9 : 6));
+    const int nout = (a.value && a.p_all) ? 7 : (a.lin ? 6 : 4);
     const int64_t S_in[11] = {n * n * kAB, n * m * kAB, n * n * kQR, m * m * kQR, n * n, n,
                               n * kQR, m * kQR, n, n * kAB, m * n * kQR};
-    const int64_t S_out[6] = {m * n * (N - 1), a.p_all ? n * n * N : n * n, n * N, m * (N - 1),
-                              m * (N - 1), a.p_all ? n * N : n};
+    const int64_t S_out[7] = {m * n * (N - 1), a.p_all ? n * n * N : n * n, n * N, m * (N - 1),
+                              m * (N - 1), a.p_all ? n * N : n, N};
     const void *in[11] = {a.A, a.B, a.Q, a.R, a.Qf, a.x0, a.q, a.r, a.qf, a.c, a.M};
-    void *out[6] = {a.K, a.P, a.X, a.U, a.d, a.p};
-    size_t off[17], total = 0;
+    void *out[7] = {a.K, a.P, a.X, a.U, a.d, a.p, a.vs};
+    size_t off[18], total = 0;
     for (int i = 0; i < nin + nout; ++i) {
         off[i] = total;
         total += ((size_t)(i < nin ? S_in[i] : S_out[i - nin]) * B * es + 255) & ~(size_t)255;
@@ -174,13 +178,14 @@ hipError_t dp_launch_soa_staged(const lqrx::DpArgs &a, hipStream_t s)
     lqrx::DpArgs a0 = a;
     a0.layout = 0;
     const void **pin[11] = {&a0.A, &a0.B, &a0.Q, &a0.R, &a0.Qf, &a0.x0, &a0.q, &a0.r, &a0.qf, &a0.c, &a0.M};
-    void **pout[6] = {&a0.K, &a0.P, &a0.X, &a0.U, &a0.d, &a0.p};
+    void **pout[7] = {&a0.K, &a0.P, &a0.X, &a0.U, &a0.d, &a0.p, &a0.vs};
     for (int i = 0; i < nin && e == hipSuccess; ++i) {        // [S][B] → [B][S]
         *pin[i] = base + off[i];
         e = lqrx::batch_transpose(in[i], base + off[i], S_in[i], B, (int)es, s);
     }
     for (int i = 0; i < nout; ++i) *pout[i] = base + off[nin + i];
     if (e == hipSuccess) e = lqrx::dp_launch(a0, s);
+    if (e == hipSuccess && J) e = lqrx::dp_value_cost_launch(a0, J, s);
     for (int i = 0; i < nout && e == hipSuccess; ++i)         // [B][S] → [S][B]
         e = lqrx::batch_transpose(base + off[nin + i], out[i], B, S_out[i], (int)es, s);
     hipError_t ef = lqrx::scratch_free(blk, s);
@@ -269,20 +274,46 @@ int check_cross_ptrs(const void *A, const void *B, const void *c, const void *Q,
     return 0;
 }
 
+// Pointer checks of lqrx_dp_solve_value[_host], in argument order (desc 1, A 2, B 3, c 4, Q 5,
+// R 6, M 7, Qf 8, x0 9, lin 10, val 11, K 12 … U 15) — before anything touches the device
+int check_value_ptrs(const void *A, const void *B, const void *c, const void *Q, const void *R,
+                     const void *M, const void *Qf, const void *x0, const lqrx_dp_linear *lin,
+                     const lqrx_dp_value *val, void *K, void *P, void *X, void *U)
+{
+    const void *in[8] = {A, B, c, Q, R, M, Qf, x0};
+    static const char *inm[8] = {"A", "B", "c", "Q", "R", "M", "Qf", "x0"};
+    for (int i = 0; i < 8; ++i)
+        if (!in[i]) return set_err(-(i + 2), "input pointer %d (%s) is NULL", i + 2, inm[i]);
+    if (!lin) return set_err(-10, "lin is NULL (pass zero q, r, qf for a problem without linear cost terms)");
+    const void *lp[5] = {lin->q, lin->r, lin->qf, lin->d, lin->p};
+    static const char *nm[5] = {"q", "r", "qf", "d", "p"};
+    for (int i = 0; i < 5; ++i)
+        if (!lp[i]) return set_err(-10, "lin->%s is NULL", nm[i]);
+    if (!val) return set_err(-11, "val is NULL (its member s is required; dV and J may be NULL)");
+    if (!val->s) return set_err(-11, "val->s is NULL");
+    const void *out[4] = {K, P, X, U};
+    for (int i = 0; i < 4; ++i)
+        if (!out[i]) return set_err(-(i + 12), "output pointer %d is NULL", i + 12);
+    return 0;
+}
+
 // lqrx_dp_solve, lqrx_dp_solve_linear (lin != NULL), lqrx_dp_solve_affine (aff: c and lin,
 // checked by check_affine_ptrs before this) and lqrx_dp_solve_cross (cross, with aff: c, M and
-// lin, checked by check_cross_ptrs); argument numbers in error codes follow the calling entry
+// lin, checked by check_cross_ptrs) and lqrx_dp_solve_value (value, with cross: val on top,
+// checked by check_value_ptrs); argument numbers in error codes follow the calling entry
 // point's signature
 int dp_solve_impl(const lqrx_dp_desc *d, const void *A, const void *B, const void *Q,
                   const void *R, const void *Qf, const void *x0, const lqrx_dp_linear *lin,
                   void *K, void *P, void *X, void *U, int32_t *info, void *stream,
                   const void *c = nullptr, bool aff = false, const void *M = nullptr,
-                  bool cross = false)
+                  bool cross = false, const lqrx_dp_value *val = nullptr, bool value = false)
 {
     int st = validate_dp(d);
     if (st) return st;
     if (d->batch == 0) return 0;
-    if (cross) {
+    if (value) {
+        if ((st = check_value_ptrs(A, B, c, Q, R, M, Qf, x0, lin, val, K, P, X, U))) return st;
+    } else if (cross) {
         if ((st = check_cross_ptrs(A, B, c, Q, R, M, Qf, x0, lin, K, P, X, U))) return st;
     } else if (aff) {
         if ((st = check_affine_ptrs(A, B, c, Q, R, Qf, x0, lin, K, P, X, U))) return st;
@@ -315,6 +346,11 @@ int dp_solve_impl(const lqrx_dp_desc *d, const void *A, const void *B, const voi
         a.cross = 1;
         a.M = M;
     }
+    if (value) {
+        a.value = 1;
+        a.vs = val->s;
+        a.vdV = val->dV;
+    }
     a.A = A; a.B = B; a.Q = Q; a.R = R; a.Qf = Qf; a.x0 = x0;
     a.K = K; a.P = P; a.X = X; a.U = U; a.info = info;
     a.n = d->n; a.m = d->m; a.N = d->N; a.dtype = d->dtype; a.p_all = d->p_mode;
@@ -323,10 +359,13 @@ int dp_solve_impl(const lqrx_dp_desc *d, const void *A, const void *B, const voi
     a.layout = d->layout;
     hipStream_t s = (hipStream_t)stream;
     hipError_t e;
-    if (d->layout == 1 && !lqrx::dp_lane_supported(d->n, d->m))
-        e = dp_launch_soa_staged(a, s);           // MFMA kernel: convert, solve, convert back
-    else
+    void *J = value ? val->J : nullptr;           // V_1(x0): one small kernel behind the solve
+    if (d->layout == 1 && !lqrx::dp_lane_supported(d->n, d->m)) {
+        e = dp_launch_soa_staged(a, s, J);        // MFMA kernel: convert, solve, convert back
+    } else {
         e = lqrx::dp_launch(a, s);
+        if (e == hipSuccess && J) e = lqrx::dp_value_cost_launch(a, J, s);
+    }
     if (e == hipErrorNotSupported)
         return set_err(LQRX_ERR_UNSUPPORTED, "no kernel for n=%d m=%d", d->n, d->m);
     if (e != hipSuccess) return hip_err(e, "dp kernel launch");
@@ -348,12 +387,14 @@ int dp_solve_host_impl(const lqrx_dp_desc *d, const void *A, const void *B, cons
                        const void *R, const void *Qf, const void *x0, const lqrx_dp_linear *lin,
                        void *K, void *P, void *X, void *U, int32_t *info,
                        const void *c = nullptr, bool aff = false, const void *M = nullptr,
-                       bool cross = false)
+                       bool cross = false, const lqrx_dp_value *val = nullptr, bool value = false)
 {
     int st = validate_dp(d);
     if (st) return st;
     if (d->batch == 0) return 0;
-    if (cross) {
+    if (value) {
+        if ((st = check_value_ptrs(A, B, c, Q, R, M, Qf, x0, lin, val, K, P, X, U))) return st;
+    } else if (cross) {
         if ((st = check_cross_ptrs(A, B, c, Q, R, M, Qf, x0, lin, K, P, X, U))) return st;
     } else if (aff && (st = check_affine_ptrs(A, B, c, Q, R, Qf, x0, lin, K, P, X, U))) return st;
     const int o = lin ? 1 : 0;
@@ -382,6 +423,13 @@ int dp_solve_host_impl(const lqrx_dp_desc *d, const void *A, const void *B, cons
         if ((st = dev_alloc(dout[i], szout[i] * s * bt, "hipMalloc output"))) return st;
     }
     if ((st = dev_alloc(dinfo, 4 * bt, "hipMalloc info"))) return st;
+    // value outputs: s (every s_k with p_mode 1), and dV, J where asked for
+    const size_t szval[3] = {d->p_mode ? N : 1, 1, 1};
+    void *hval[3] = {value ? val->s : nullptr, value ? val->dV : nullptr, value ? val->J : nullptr};
+    DevBuf dval[3];
+    for (int i = 0; i < 3; ++i)
+        if (hval[i] && (st = dev_alloc(dval[i], szval[i] * s * bt, "hipMalloc value output"))) return st;
+    const lqrx_dp_value dv{dval[0].p, dval[1].p, dval[2].p};
     lqrx_dp_linear dl{};
     if (lin) {
         dl.q = din[6].p; dl.r = din[7].p; dl.qf = din[8].p; dl.d = dout[4].p; dl.p = dout[5].p;
@@ -389,11 +437,16 @@ int dp_solve_host_impl(const lqrx_dp_desc *d, const void *A, const void *B, cons
     st = dp_solve_impl(d, din[0].p, din[1].p, din[2].p, din[3].p, din[4].p, din[5].p,
                        lin ? &dl : nullptr, dout[0].p, dout[1].p, dout[2].p, dout[3].p,
                        (int32_t *)dinfo.p, nullptr, aff ? din[9].p : nullptr, aff,
-                       cross ? din[10].p : nullptr, cross);
+                       cross ? din[10].p : nullptr, cross, value ? &dv : nullptr, value);
     if (st < 0) return st;
     for (int i = 0; i < nout; ++i) {
         hipError_t e = hipMemcpy(hout[i], dout[i].p, szout[i] * s * bt, hipMemcpyDeviceToHost);
         if (e != hipSuccess) return hip_err(e, "D2H");
+    }
+    for (int i = 0; i < 3; ++i) {
+        if (!hval[i]) continue;
+        hipError_t e = hipMemcpy(hval[i], dval[i].p, szval[i] * s * bt, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return hip_err(e, "D2H value");
     }
     if (info) {
         hipError_t e = hipMemcpy(info, dinfo.p, 4 * bt, hipMemcpyDeviceToHost);
@@ -546,6 +599,25 @@ int lqrx_dp_solve_cross_host(const lqrx_dp_desc *d, const void *A, const void *B
                              void *U, int32_t *info)
 {
     return dp_solve_host_impl(d, A, B, Q, R, Qf, x0, lin, K, P, X, U, info, c, true, M, true);
+}
+
+// the value function's constant on top of the cross solve: s, dV = Σ hᵀd, J = V_1(x0) (see lqrx.h)
+int lqrx_dp_solve_value(const lqrx_dp_desc *d, const void *A, const void *B, const void *c,
+                        const void *Q, const void *R, const void *M, const void *Qf, const void *x0,
+                        const lqrx_dp_linear *lin, const lqrx_dp_value *val, void *K, void *P,
+                        void *X, void *U, int32_t *info, void *stream)
+{
+    return dp_solve_impl(d, A, B, Q, R, Qf, x0, lin, K, P, X, U, info, stream, c, true, M, true,
+                         val, true);
+}
+
+int lqrx_dp_solve_value_host(const lqrx_dp_desc *d, const void *A, const void *B, const void *c,
+                             const void *Q, const void *R, const void *M, const void *Qf,
+                             const void *x0, const lqrx_dp_linear *lin, const lqrx_dp_value *val,
+                             void *K, void *P, void *X, void *U, int32_t *info)
+{
+    return dp_solve_host_impl(d, A, B, Q, R, Qf, x0, lin, K, P, X, U, info, c, true, M, true, val,
+                              true);
 }
 
 

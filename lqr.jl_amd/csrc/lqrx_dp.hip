@@ -698,8 +698,19 @@ __device__ __forceinline__ void dp_rollout_full(const DpArgs &a, int64_t b, T *l
 //                cache-resident m·n block of the trajectory otherwise (no LDS image: LDS decides
 //                the workgroups per CU on the fp64 2×1 grid and above) — issued
 //                behind the PB / PA products, beside Q, so that it lands under the E product.
+//   VAR_VALUE  : the value function's constant (lqrx_dp_solve_value), only with VAR_LIN | VAR_AFF |
+//                VAR_CROSS, with or without VAR_TV: s_k = s_{k+1} + c_kᵀ(p + ½Pc_k) − ½h_kᵀd_k and
+//                dV = Σ h_kᵀd_k.  Two per-lane accumulators on lanes 0–15, the lanes that hold p, Pc,
+//                w and d in column layout: sc += c_i(p_i + ½(Pc)_i) in aff_ptilde(), hd += w_j d_j
+//                where d is formed.  They live in 2·16 LDS slots behind the c image, each touched
+//                by its own lane only (no barrier): as loop-carried registers they spilled 4 VGPRs
+//                (20 B/lane) on the fp64 2×1 grid at 2 waves/SIMD, which has none to spare
+//                (DESIGN §3.7).  No cross-lane work in the
+//                knot loop unless every s_k is asked for (a.p_all, uniform over the grid); one
+//                16-lane reduction of the running sums either way, so s_1 is the same bits in
+//                both modes.
 enum : int { VAR_NOSOLVE = 2, VAR_NOROLL = 4, VAR_NOKSTORE = 8, VAR_SWEEPONLY = 16, VAR_TV = 32,
-             VAR_LIN = 64, VAR_AFF = 128, VAR_CROSS = 256 };
+             VAR_LIN = 64, VAR_AFF = 128, VAR_CROSS = 256, VAR_VALUE = 512 };
 
 // Vector products with register tiles (VAR_LIN).  A vector v is read from its LDS image in
 // "row layout" (lane l, slot [i][r] = v[16i + Tile::row(l, r)], the rows a C-layout tile's
@@ -731,6 +742,16 @@ __device__ __forceinline__ T lin_rowsum(T x)
     return x + __shfl_xor(x, 32);
 }
 
+// sum over lanes 0–15 of a 16-lane group (VAR_VALUE: the column-layout partials)
+template <typename T>
+__device__ __forceinline__ T lin_colsum(T x)
+{
+    x += __shfl_xor(x, 8);
+    x += __shfl_xor(x, 4);
+    x += __shfl_xor(x, 2);
+    return x + __shfl_xor(x, 1);
+}
+
 template <typename T, int NT, int MT, int WAVES, int VAR, bool FULL>
 __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
 {
@@ -740,7 +761,8 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
     constexpr bool TV = (VAR & VAR_TV) != 0, LIN = (VAR & VAR_LIN) != 0, AFF = (VAR & VAR_AFF) != 0;
     static_assert(!AFF || LIN, "VAR_AFF extends VAR_LIN");
     constexpr bool CROSS = (VAR & VAR_CROSS) != 0;
-    static_assert(!CROSS || (LIN && AFF), "VAR_CROSS extends VAR_LIN | VAR_AFF");
+    constexpr bool VALUE = (VAR & VAR_VALUE) != 0;
+    static_assert(!VALUE || CROSS, "VAR_VALUE extends VAR_LIN | VAR_AFF | VAR_CROSS");
     // Q + AᵀPA in the shadow of the Newton–Schulz chain (PnShadow): time-invariant A only
     constexpr bool SHADOW = !TV && (VAR & (VAR_NOSOLVE | VAR_SWEEPONLY)) == 0;
     constexpr int NP = C::NP;
@@ -748,7 +770,9 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
     // p (NP), then w / d (MP); time-invariant q (NP), r (MP) images after them; VAR_AFF: one more
     // NP slot, the time-invariant c image
     constexpr int CIMG = TV ? NP + MP : 2 * (NP + MP);
-    __shared__ T vimg[LIN ? CIMG + (AFF ? NP : 0) : 1];
+    // VAR_VALUE: 16 + 16 accumulator slots (sc, hd) behind it
+    constexpr int VIMG = CIMG + (AFF ? NP : 0);
+    __shared__ T vimg[LIN ? VIMG + (VALUE ? 32 : 0) : 1];
     // Q (time-invariant, read every knot as the P_ accumulator start) lives in LDS for the
     // horizon: an LDS read per element instead of an L2 round trip per knot
     __shared__ T qimg[TV ? 1 : C::QIMG];
@@ -813,6 +837,9 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
         if constexpr (!TV) {
             for (int i = lane; i < MP; i += 64) vimg[2 * NP + MP + i] = i < m ? rg[i] : (T)0;
         }
+        if constexpr (VALUE) {
+            if (lane < 32) vimg[VIMG + lane] = (T)0;
+        }
         __syncthreads();
     }
     acc Xi[MT][MT], Xp[MT][MT], Id[MT][MT];     // E⁻¹ of the last two knots, identity tiles
@@ -829,6 +856,10 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
     // per-trajectory values of the knot loop, formed once: the symmetrize's diagonal-tile LDS
     // indices (kept opaque so that they stay in registers and are not re-derived per knot)
     const bool ns_off = a.ns_off != 0;
+    // VAR_VALUE: every s_k (p_all) at N per trajectory, s_N = 0
+    if constexpr (VALUE) {
+        if (a.p_all && lane == 0) ((T *)a.vs)[(size_t)b * (size_t)N + (N - 1)] = (T)0;
+    }
     int didx[4];
     symmetrize_diag_index<T, NT>(didx, lane);
 #pragma unroll
@@ -870,6 +901,17 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
                     crow[i][r] = (FULL || e < n) ? cg[(size_t)(k - 1) * sc + e] : (T)0;
                 }
         }
+        // VAR_VALUE, time-varying: c_k once more in column layout (lanes 0–15), issued here with the
+        // row-layout read so that it lands under the knot's products; read where aff_ptilde() uses it,
+        // it was an exposed HBM round trip per knot (+5.5 ms of 43 at n = 32, m = 16, B = 16384)
+        T ccol[(VALUE && TV) ? NT : 1];
+        if constexpr (VALUE && TV) {
+#pragma unroll
+            for (int j = 0; j < NT; ++j) {
+                const int i = 16 * j + lane;
+                ccol[j] = (lane < 16 && (FULL || i < n)) ? cg[(size_t)(k - 1) * sc + i] : (T)0;
+            }
+        }
         // VAR_AFF: p̃ = p + P c_k, in place in the p image (the image is rewritten whole at the end
         // of the knot).  Every lane's reads of p from the knot before are behind that knot's closing
         // barrier, and slot 16j + lane was last written by this lane, so one barrier — after the
@@ -900,7 +942,21 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
 #pragma unroll
                 for (int j = 0; j < NT; ++j) {
                     const T s = lin_rowsum(pc[j]);
-                    if (lane < 16) vimg[16 * j + lane] += s;
+                    if constexpr (VALUE) {
+                        // c_i (p_i + ½(Pc)_i) from the slot before the add; c_i in column layout:
+                        // the c image, or ccol (time-varying)
+                        if (lane < 16) {
+                            const int i = 16 * j + lane;
+                            T ci;
+                            if constexpr (TV) ci = ccol[j];
+                            else ci = vimg[CIMG + i];
+                            const T pi = vimg[i];
+                            vimg[VIMG + lane] = fma(ci, fma((T)0.5, s, pi), vimg[VIMG + lane]);
+                            vimg[i] = pi + s;
+                        }
+                    } else {
+                        if (lane < 16) vimg[16 * j + lane] += s;
+                    }
                 }
                 __syncthreads();                       // p̃ complete before the row-layout read
             }
@@ -1058,6 +1114,10 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
                     dv[j] = lin_rowsum(dv[j]);
                     const int i = 16 * j + lane;
                     if (lane < 16) {
+                        // h_kᵀd_k partial: w_i from its slot (behind the barrier above), before d
+                        // lands there — not from w[j], which would stay live across Xᵀw
+                        if constexpr (VALUE)
+                            vimg[VIMG + 16 + lane] = fma(vimg[NP + i], dv[j], vimg[VIMG + 16 + lane]);
                         vimg[NP + i] = dv[j];
                         if (i < m) dg[(size_t)(k - 1) * m + i] = dv[j];
                     }
@@ -1085,11 +1145,32 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
 #pragma unroll
             for (int j = 0; j < NT; ++j) P[i][j] = Pn[i][j];
         if (Pall) tiles_store<T, NT, NT>(P, Pall + (size_t)(k - 1) * nn, n, n, n, lane);
+        if constexpr (VALUE) {
+            // every s_k: the running sums reduced, not the increments (a.p_all is a kernel argument:
+            // the branch is uniform over the grid).  Each lane reads its own two slots, so no
+            // barrier; here, behind the knot's last product, G and K are dead — between d and
+            // −GᵀK the branch spilled 2 VGPRs on the fp64 2×1 grid at 2 waves/SIMD
+            if (a.p_all) {
+                const T vsc = lane < 16 ? vimg[VIMG + lane] : (T)0;
+                const T vhd = lane < 16 ? vimg[VIMG + 16 + lane] : (T)0;
+                const T sk = lin_colsum(vsc) - (T)0.5 * lin_colsum(vhd);
+                if (lane == 0) ((T *)a.vs)[(size_t)b * (size_t)N + (k - 1)] = sk;
+            }
+        }
     }
     if (!a.p_all) tiles_store<T, NT, NT>(P, (T *)a.P + (size_t)b * nn, n, n, n, lane);
     if (a.info && lane == 0) a.info[b] = info;
     if constexpr (LIN) {
         if (!a.p_all && lane < n) ((T *)a.p)[(size_t)b * n + lane] = vimg[lane];   // p_1
+    }
+    if constexpr (VALUE) {
+        const T vsc = lane < 16 ? vimg[VIMG + lane] : (T)0;
+        const T vhd = lane < 16 ? vimg[VIMG + 16 + lane] : (T)0;
+        const T rsc = lin_colsum(vsc), rhd = lin_colsum(vhd);
+        if (lane == 0) {
+            if (!a.p_all) ((T *)a.vs)[b] = rsc - (T)0.5 * rhd;    // s_1
+            if (a.vdV) ((T *)a.vdV)[b] = rhd;
+        }
     }
 
     if constexpr ((VAR & VAR_NOROLL) == 0) {
@@ -1734,7 +1815,10 @@ static hipError_t launch_dp_tv(const DpArgs &a, hipStream_t s)
     // 1×1 (double) and up to 2×1 (float) grids; time-invariant LIN keeps the plain kernel's
     // occupancy (its vector work sits after the solve, where fewer tiles are live)
     constexpr int LW = (NT * MT <= (sizeof(T) == 4 ? 2 : 1)) ? 2 : 1;
-    // cost cross term (needs lin and aff): the launch bounds of the affine variants
+    // value-function constant (needs lin, aff and cross): the launch bounds of the cross variants
+    if (a.value && (a.tv_AB || a.tv_QR))
+        return launch_dp<T, NT, MT, LW, VAR_TV | VAR_LIN | VAR_AFF | VAR_CROSS | VAR_VALUE>(a, s);
+    if (a.value) return launch_dp<T, NT, MT, WAVES, VAR_LIN | VAR_AFF | VAR_CROSS | VAR_VALUE>(a, s);
     if (a.cross && (a.tv_AB || a.tv_QR)) return launch_dp<T, NT, MT, LW, VAR_TV | VAR_LIN | VAR_AFF | VAR_CROSS>(a, s);
     if (a.cross) return launch_dp<T, NT, MT, WAVES, VAR_LIN | VAR_AFF | VAR_CROSS>(a, s);
     // affine offset (needs lin): the launch bounds of the linear-terms variants
@@ -1798,6 +1882,44 @@ bool dp_supported(int dtype, int n, int m, bool tv)
     if (dp_lane_supported(n, m)) return true;
     const int nt = (n + 15) / 16, mt = (m + 15) / 16;
     return (n >= 1 && m >= 1 && nt <= 4 && mt <= 2) || dp_big_supported(n, m);
+}
+
+// ------------------------------------------------------------------ J = V_1(x0)
+// dp_value_cost_kernel<T> — behind a value solve of any family, on its outputs: one thread per
+// trajectory reads P_1 (symmetric, column-major n×n), p_1, s_1 and x0, accumulates
+// ½x0ᵀP_1x0 + p_1ᵀx0 + s_1 in double and rounds to T.  Element e of trajectory b sits at
+// [b·S + e] (layout 0, S the array's elements per trajectory) or [e·batch + b] (layout 1); with
+// p_all, P_1 / p_1 / s_1 are element block 0 of N.  n² + 2n + 1 loads per trajectory: the solve
+// itself moved (N−1)·(mn + n + m) and more.
+template <typename T>
+__global__ __launch_bounds__(256) void dp_value_cost_kernel(const DpArgs a, T *__restrict__ J)
+{
+    const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (b >= a.batch) return;
+    const int n = a.n;
+    const int64_t kP = a.p_all ? a.N : 1;
+    const bool soa = a.layout == 1;
+    const int64_t es = soa ? a.batch : 1;                       // element stride
+    const T *P = (const T *)a.P + (soa ? b : b * (int64_t)n * n * kP);
+    const T *p = (const T *)a.p + (soa ? b : b * (int64_t)n * kP);
+    const T *x = (const T *)a.x0 + (soa ? b : b * (int64_t)n);
+    const T *sv = (const T *)a.vs;
+    double acc = a.p_all ? (double)sv[soa ? b : b * kP] : (double)sv[b];   // s_1
+    for (int j = 0; j < n; ++j) {
+        const double xj = (double)x[j * es];
+        double col = 0.0;
+        for (int i = 0; i < n; ++i) col += (double)P[((int64_t)j * n + i) * es] * (double)x[i * es];
+        acc += xj * (0.5 * col + (double)p[j * es]);
+    }
+    J[b] = (T)acc;
+}
+
+hipError_t dp_value_cost_launch(const DpArgs &a, void *J, hipStream_t s)
+{
+    dim3 grid((unsigned)((a.batch + 255) / 256)), block(256);
+    if (a.dtype == 0) hipLaunchKernelGGL((dp_value_cost_kernel<double>), grid, block, 0, s, a, (double *)J);
+    else hipLaunchKernelGGL((dp_value_cost_kernel<float>), grid, block, 0, s, a, (float *)J);
+    return hipGetLastError();
 }
 
 } // namespace lqrx

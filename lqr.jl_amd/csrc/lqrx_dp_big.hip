@@ -16,7 +16,10 @@
 // knot, before w = r + Bᵀp, and x_{k+1} += c_k in the rollout; the cost cross term M_k of
 // lqrx_dp_solve_cross (a.cross, with a.lin and a.aff): K ← BᵀPA starts from M_k (wg_mm's C
 // argument, as E starts from R) and Mᵀ_k is added into APB, so that APB·K and APB·d are Gᵀ· with
-// G = BᵀPA + M_k.
+// G = BᵀPA + M_k; the value function's constant of lqrx_dp_solve_value (a.value, with a.cross):
+// per-thread running partials of c_kᵀ(p + ½Pc_k) (where p̃ is formed) and of wᵀd (behind the
+// solves), summed over the workgroup by wg_sum — once after the knot loop, or at every knot when
+// every s_k is asked for (a.p_all).
 #include "lqrx_internal.h"
 #include "lqrx_tile.h"
 #include "lqrx_wg.h"
@@ -31,6 +34,21 @@ namespace {
 using wg::BT;
 using wg::Mat;
 
+
+// Sum of x over the workgroup's BT threads, returned to every thread: xor-shuffles inside each
+// wave, then the four wave sums through LDS in a fixed order.  Two barriers; call it uniformly.
+template <typename T> __device__ T wg_sum(T x, T *red, int tid)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o);
+    __syncthreads();                                            // red free of its previous readers
+    if ((tid & 63) == 0) red[tid >> 6] = x;
+    __syncthreads();
+    T s = red[0];
+#pragma unroll
+    for (int w = 1; w < BT / 64; ++w) s += red[w];
+    return s;
+}
 
 template <typename T>
 __global__ __launch_bounds__(BT) void dp_big_kernel(const DpArgs a, T *__restrict__ ws, size_t ws_elems, int64_t b0)
@@ -52,6 +70,12 @@ __global__ __launch_bounds__(BT) void dp_big_kernel(const DpArgs a, T *__restric
     const bool cross = aff && a.cross != 0;
     const size_t sM = a.tv_QR ? nm : 0;
     const T *M0 = cross ? (const T *)a.M + b * nm * kQR : nullptr;
+    // value-function constant: this thread's running partials; every s_k with p_all (s_N = 0)
+    const bool value = cross && a.value != 0;
+    T vsc = 0, vhd = 0;
+    T *sall = (value && a.p_all) ? (T *)a.vs + (size_t)b * (size_t)N : nullptr;
+    __shared__ T s_red[BT / 64];
+    if (sall && tid == 0) sall[N - 1] = 0;
 
     T *w0 = ws + (size_t)blockIdx.x * ws_elems;
     T *P = w0, *Pn = P + nn, *PA = Pn + nn, *PB = PA + nn, *APB = PB + nm, *E = APB + nm;
@@ -92,6 +116,7 @@ __global__ __launch_bounds__(BT) void dp_big_kernel(const DpArgs a, T *__restric
             for (int i = tid; i < n; i += BT) {
                 T s = 0;
                 for (int j = 0; j < n; ++j) s += P[i + (size_t)j * n] * c[j];
+                if (value) vsc += c[i] * (pv[i] + (T)0.5 * s);  // c_i (p_i + ½(Pc)_i), p before the add
                 pv[i] += s;
             }
             __syncthreads();
@@ -149,8 +174,14 @@ __global__ __launch_bounds__(BT) void dp_big_kernel(const DpArgs a, T *__restric
                 for (int c = 0; c < m; ++c) s2 += APB[i + (size_t)c * n] * dk[c];
                 pn[i] = q[i] + s1 - s2;
             }
+            if (value)                                          // h_kᵀd_k partial: w is intact, d solved
+                for (int c = tid; c < m; c += BT) vhd += wv[c] * dk[c];
         }
         __syncthreads();
+        if (sall) {                                             // uniform: a kernel argument
+            const T sk = wg_sum<T>(vsc, s_red, tid) - (T)0.5 * wg_sum<T>(vhd, s_red, tid);
+            if (tid == 0) sall[k - 1] = sk;
+        }
         // :63 P .= P_
         { T *t = P; P = Pn; Pn = t; }
         if (lin) { T *t = pv; pv = pn; pn = t; }
@@ -169,6 +200,13 @@ __global__ __launch_bounds__(BT) void dp_big_kernel(const DpArgs a, T *__restric
     }
     __syncthreads();
     if (tid == 0 && a.info) a.info[b] = s_info;
+    if (value) {                                                // uniform: a kernel argument
+        const T rsc = wg_sum<T>(vsc, s_red, tid), rhd = wg_sum<T>(vhd, s_red, tid);
+        if (tid == 0) {
+            if (!a.p_all) ((T *)a.vs)[b] = rsc - (T)0.5 * rhd;  // s_1
+            if (a.vdV) ((T *)a.vdV)[b] = rhd;
+        }
+    }
 
     // :66-70 rollout  u_k = −K_k x_k (− d_k),  x_{k+1} = A x_k + B u_k
     T *X = (T *)a.X + (size_t)b * (size_t)N * n, *U = (T *)a.U + (size_t)b * (size_t)(N - 1) * m;

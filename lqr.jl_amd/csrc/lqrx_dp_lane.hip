@@ -57,7 +57,11 @@ __device__ __forceinline__ void lane_load(T (&D)[RP][CP], const T *__restrict__ 
 // from the lower triangle of P_{k+1}), and the rollout adds c_k to x_{k+1}.
 // CROSS (cost cross term uᵀM_k x, lqrx_dp_solve_cross; needs LIN and AFF; M follows Q, R: per
 // knot with TV and tv_QR, prefetched with them): G = BᵀPA + M_k — G[c][j] starts from M[c][j].
-template <typename T, int NP, int MP, bool TV, bool SOA, bool LIN = false, bool AFF = false, bool CROSS = false>
+// VALUE (the value function's constant, lqrx_dp_solve_value; needs LIN, AFF and CROSS): two
+// scalars in the lane's registers, vsc += c_kᵀ(p + ½Pc_k) where p̃ is formed and vhd += h_kᵀd_k
+// where d is; s_k = vsc − ½vhd (stored per knot with p_all), dV = vhd.
+template <typename T, int NP, int MP, bool TV, bool SOA, bool LIN = false, bool AFF = false, bool CROSS = false,
+          bool VALUE = false>
 __global__ __launch_bounds__(64) void dp_lane_kernel(const DpArgs a)
 {
     const int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x;
@@ -123,6 +127,12 @@ __global__ __launch_bounds__(64) void dp_lane_kernel(const DpArgs a)
     const T *Mb = CROSS ? (const T *)a.M + tb(nm * kQR) : nullptr;
     T Mx[XM][XN];
     if constexpr (CROSS && !TV) lane_load<T, MP, NP>(Mx, Mb, m, n, (T)0, es);   // time-invariant M: loaded once
+    static_assert(!VALUE || CROSS, "VALUE extends LIN && AFF && CROSS");
+    T vsc = (T)0, vhd = (T)0;
+    T *sall = (VALUE && a.p_all) ? (T *)a.vs + tb(N) : nullptr;
+    if constexpr (VALUE) {
+        if (sall) sall[(int64_t)(N - 1) * es] = (T)0;            // s_N = 0
+    }
     if constexpr (LIN) {
         const T *qf = (const T *)a.qf + tb(n);
 #pragma unroll
@@ -212,6 +222,12 @@ __global__ __launch_bounds__(64) void dp_lane_kernel(const DpArgs a)
                 T s = pv[i];
 #pragma unroll
                 for (int l = 0; l < NP; ++l) s = fma(PS(i, l), cv[l], s);
+                if constexpr (VALUE) {                           // c_i (p_i + ½(Pc)_i), p before the add
+                    T t = (T)0;
+#pragma unroll
+                    for (int l = 0; l < NP; ++l) t = fma(PS(i, l), cv[l], t);
+                    vsc = fma(cv[i], fma((T)0.5, t, pv[i]), vsc);
+                }
                 pv[i] = s;
             }
         }
@@ -301,12 +317,14 @@ __global__ __launch_bounds__(64) void dp_lane_kernel(const DpArgs a)
         if constexpr (LIN) {
             // d = E⁻¹(r + Bᵀp): the potrs of :30 on one more column
             T y[MP], dv[MP];
+            T hv[VALUE ? MP : 1];
 #pragma unroll
             for (int i = 0; i < MP; ++i) {
                 T s = (T)0;
 #pragma unroll
                 for (int l = 0; l < NP; ++l) s = fma(B[l][i], pv[l], s);
                 s = rv[i] + s;
+                if constexpr (VALUE) hv[i] = s;                  // h = r + Bᵀp̃
 #pragma unroll
                 for (int c = 0; c < i; ++c) s = fma(-L[i][c], y[c], s);
                 y[i] = s * Linv[i];
@@ -321,6 +339,11 @@ __global__ __launch_bounds__(64) void dp_lane_kernel(const DpArgs a)
 #pragma unroll
             for (int i = 0; i < MP; ++i)
                 if (i < m) db[((int64_t)(k - 1) * m + i) * es] = dv[i];
+            if constexpr (VALUE) {
+#pragma unroll
+                for (int i = 0; i < MP; ++i) vhd = fma(hv[i], dv[i], vhd);
+                if (sall) sall[(int64_t)(k - 1) * es] = vsc - (T)0.5 * vhd;   // s_k
+            }
             // p ← q + Aᵀp − APB·d  (APB[i][c] = G[c][i])
             T pn[NP];
 #pragma unroll
@@ -361,6 +384,10 @@ __global__ __launch_bounds__(64) void dp_lane_kernel(const DpArgs a)
             for (int i = 0; i < NP; ++i)
                 if (i < n) p1[i * es] = pv[i];
         }
+    }
+    if constexpr (VALUE) {
+        if (!a.p_all) ((T *)a.vs)[b] = vsc - (T)0.5 * vhd;       // s_1
+        if (a.vdV) ((T *)a.vdV)[b] = vhd;
     }
 
     // forward rollout  :66-70  u_k = −K_k x_k ; x_{k+1} = A_k x_k + B_k u_k
@@ -1072,7 +1099,12 @@ static hipError_t launch_lane(const DpArgs &a, hipStream_t s)
     dim3 grid((unsigned)((a.batch + 63) / 64)), block(64);
     const bool tv = a.tv_AB || a.tv_QR, soa = a.layout == 1;
     if (a.cross && !(a.lin && a.aff)) return hipErrorInvalidValue;   // the cross term extends the affine solve
-    if (a.cross && tv && soa) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, true, true, true, true, true>), grid, block, 0, s, a);
+    if (a.value && !a.cross) return hipErrorInvalidValue;              // the constant extends the cross solve
+    if (a.value && tv && soa) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, true, true, true, true, true, true>), grid, block, 0, s, a);
+    else if (a.value && tv) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, true, false, true, true, true, true>), grid, block, 0, s, a);
+    else if (a.value && soa) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, false, true, true, true, true, true>), grid, block, 0, s, a);
+    else if (a.value) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, false, false, true, true, true, true>), grid, block, 0, s, a);
+    else if (a.cross && tv && soa) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, true, true, true, true, true>), grid, block, 0, s, a);
     else if (a.cross && tv) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, true, false, true, true, true>), grid, block, 0, s, a);
     else if (a.cross && soa) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, false, true, true, true, true>), grid, block, 0, s, a);
     else if (a.cross) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, false, false, true, true, true>), grid, block, 0, s, a);

@@ -37,9 +37,18 @@ struct DpArgs {
     // otherwise.  G = BᵀPA + M_k.  (Appended: every earlier field keeps its offset.)
     int cross;
     const void *M;
+    // value-function constant (lqrx_dp_solve_value; needs lin = aff = cross = 1): vs receives s_1
+    // (batch) or, with p_all, every s_k (N per trajectory, knot k at k−1, s_N = 0; layout as p);
+    // vdV, if not null, Σ_k h_kᵀd_k (batch).  Batch vectors are the same in both layouts.
+    // (Appended: every earlier field keeps its offset.)
+    int value;
+    void *vs, *vdV;
 };
 
 hipError_t dp_launch(const DpArgs &a, hipStream_t s);
+// J = V_1(x0) = ½x0ᵀP_1x0 + p_1ᵀx0 + s_1 behind a value solve (lqrx_dp.hip): one thread per
+// trajectory on a's P, p, vs and x0 in a's layout, accumulated in double, written to J (batch)
+hipError_t dp_value_cost_launch(const DpArgs &a, void *J, hipStream_t s);
 // out = inᵀ for a rows × cols row-major matrix of 4- or 8-byte elements (lqrx_layout.hip):
 // layout 1 (SoA, [S][batch]) ↔ layout 0 ([batch][S]) for the kernels that need layout 0
 hipError_t batch_transpose(const void *in, void *out, int64_t rows, int64_t cols, int elem_bytes, hipStream_t s);

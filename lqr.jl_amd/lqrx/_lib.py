@@ -34,6 +34,12 @@ class DpLinear(C.Structure):
                 ("d", C.c_void_p), ("p", C.c_void_p)]
 
 
+class DpValue(C.Structure):
+    """Mirror of ``lqrx_dp_value`` (value-function constant: s required; dV, J optional, all out)."""
+
+    _fields_ = [("s", C.c_void_p), ("dV", C.c_void_p), ("J", C.c_void_p)]
+
+
 class KktDesc(C.Structure):
     """Mirror of ``lqrx_kkt_desc``."""
 
@@ -98,6 +104,10 @@ _SIGS = {
                             + [_VP] * 4 + [_VP, _VP]),
     "lqrx_dp_solve_cross_host": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 8
                                  + [C.POINTER(DpLinear)] + [_VP] * 5),
+    "lqrx_dp_solve_value": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 8 + [C.POINTER(DpLinear)]
+                            + [C.POINTER(DpValue)] + [_VP] * 4 + [_VP, _VP]),
+    "lqrx_dp_solve_value_host": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 8
+                                 + [C.POINTER(DpLinear)] + [C.POINTER(DpValue)] + [_VP] * 5),
     "lqrx_dp_solve_host_devices": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 10 + [_VP, _VP, C.c_int32]),
     "lqrx_dp_solve_linear_host_devices": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 6 + [C.POINTER(DpLinear)]
                                           + [_VP] * 5 + [_VP, C.c_int32]),

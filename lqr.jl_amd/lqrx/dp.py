@@ -10,7 +10,9 @@ Reference surface (Julia, /root/reference/src):
 Extension (no upstream counterpart): linear cost terms q, r, qf on
 LQRProblem / LQRBatch → feedforward d and linear cost-to-go p (lqrx_dp_solve_linear); an
 affine dynamics offset c, x⁺ = A x + B u + c (lqrx_dp_solve_affine), which also returns d, p; a
-cost cross term uᵀM x (lqrx_dp_solve_cross), G = BᵀPA + M, on top of both.
+cost cross term uᵀM x (lqrx_dp_solve_cross), G = BᵀPA + M, on top of both; the value function's
+constant s_k, the expected reduction dV = Σ h_kᵀd_k and the optimal cost J = V_1(x0)
+(lqrx_dp_solve_value, value=True) on top of all three.
 
 Array conventions here: a single problem uses plain (rows, cols) numpy matrices; batches
 use numpy arrays shaped (batch, rows, cols).  The C ABI wants Julia column-major with the
@@ -106,15 +108,21 @@ class LQRSolution:
     info: int = 0
     d: np.ndarray | None = None   # feedforward (linear terms): u_k = −K_k x_k − d_k
     p: np.ndarray | None = None   # linear cost-to-go p_1 (or every p_k with all_P)
+    # value-function constant (of(…, value=True)): s = s_1 (or every s_k with all_P, s_N = 0),
+    # dV = Σ h_kᵀd_k (the expected reduction of a line search), J = V_1(x0) (the optimal cost)
+    s: np.ndarray | None = None
+    dV: np.ndarray | None = None
+    J: np.ndarray | None = None
 
     @classmethod
-    def of(cls, prob: LQRProblem, all_P: bool = False):
+    def of(cls, prob: LQRProblem, all_P: bool = False, value: bool = False):
         n, m, N = prob.size()
-        lin = prob.q is not None or prob.c is not None or prob.M is not None
+        lin = prob.q is not None or prob.c is not None or prob.M is not None or value
+        val = dict(s=np.zeros(N) if all_P else np.zeros(()), dV=np.zeros(()), J=np.zeros(())) if value else {}
         return cls(np.zeros((N - 1, m, n)), np.zeros((N, n)), np.zeros((N - 1, m)),
                    np.zeros((N, n, n)) if all_P else np.zeros((n, n)),
                    d=np.zeros((N - 1, m)) if lin else None,
-                   p=(np.zeros((N, n)) if all_P else np.zeros(n)) if lin else None)
+                   p=(np.zeros((N, n)) if all_P else np.zeros(n)) if lin else None, **val)
 
 
 @dataclass
@@ -204,7 +212,7 @@ def _devices(devices):
 
 
 def solve_batch(b: LQRBatch, dtype: int = _lib.F64, all_P: bool = False, layout: int = 0,
-                devices=None):
+                devices=None, value: bool = False):
     """Batched solve! through lqrx_dp_solve_host.  Returns dict of logical arrays
     K (batch, N-1, m, n), P (batch, n, n) or (batch, N, n, n), X (batch, N, n),
     U (batch, N-1, m), info (batch,), and the ABI return code.  layout = 1 hands the
@@ -213,11 +221,20 @@ def solve_batch(b: LQRBatch, dtype: int = _lib.F64, all_P: bool = False, layout:
     GPUs in one call (lqrx_dp_solve[_linear]_host_devices; repeats allowed).  With b.c (affine
     dynamics) the call is lqrx_dp_solve_affine_host: missing q, r, qf are zeros, d and p are
     returned; it has no devices= form.  With b.M (cost cross term) the call is
-    lqrx_dp_solve_cross_host: a missing c is zeros as well; no devices= form either."""
+    lqrx_dp_solve_cross_host: a missing c is zeros as well; no devices= form either.  With
+    value=True the call is lqrx_dp_solve_value_host: missing c, M, q, r, qf are zeros, and the
+    result gains s ((batch,) s_1, or (batch, N) every s_k with all_P), dV and J ((batch,)); no
+    devices= form."""
     n, m, N = b.size()
     bt = b.batch
     tvAB, tvQR = b.time_varying()
     npdt = np.float64 if dtype == _lib.F64 else np.float32
+    if value:
+        if devices is not None:
+            raise ValueError("devices= is not available with value=True")
+        if b.M is None:
+            b = LQRBatch(b.A, b.B, b.Q, b.R, b.Qf, b.x0, b.N, b.extra, q=b.q, r=b.r, qf=b.qf, c=b.c,
+                         M=np.zeros((bt, N - 1, m, n) if tvQR else (bt, m, n), npdt))
     cross = b.M is not None
     aff = b.c is not None or cross
     if cross:
@@ -277,8 +294,15 @@ def solve_batch(b: LQRBatch, dtype: int = _lib.F64, all_P: bool = False, layout:
                 Mv = to_abi(np.asarray(b.M, dtype=npdt)).reshape(-1)
                 if layout == 1:
                     Mv = to_soa(Mv, bt)
-                rc = _lib.check(lib.lqrx_dp_solve_cross_host(*args[:3], _ptr(cv), *args[3:5], _ptr(Mv),
-                                                             *args[5:]))
+                if value:   # val follows lin: argument 11
+                    sv = np.zeros(bt * (N if all_P else 1), npdt)
+                    dVv, Jv = np.zeros(bt, npdt), np.zeros(bt, npdt)
+                    vl = _lib.DpValue(_ptr(sv).value, _ptr(dVv).value, _ptr(Jv).value)
+                    rc = _lib.check(lib.lqrx_dp_solve_value_host(*args[:3], _ptr(cv), *args[3:5], _ptr(Mv),
+                                                                 *args[5:8], C.byref(vl), *args[8:]))
+                else:
+                    rc = _lib.check(lib.lqrx_dp_solve_cross_host(*args[:3], _ptr(cv), *args[3:5], _ptr(Mv),
+                                                                 *args[5:]))
             else:
                 rc = _lib.check(lib.lqrx_dp_solve_affine_host(*args[:3], _ptr(cv), *args[3:]))
         elif devices is None:
@@ -298,27 +322,35 @@ def solve_batch(b: LQRBatch, dtype: int = _lib.F64, all_P: bool = False, layout:
         K, P, X, U = (from_soa(a, bt) for a in (K, P, X, U))
         if lin:
             dff, pv = from_soa(dff, bt), from_soa(pv, bt)
+        if value and all_P:
+            sv = from_soa(sv, bt)
     out = dict(K=from_abi(K, (bt, N - 1, m, n)),
                P=from_abi(P, (bt, N, n, n) if all_P else (bt, n, n)),
                X=X.reshape(bt, N, n), U=U.reshape(bt, N - 1, m), info=info, rc=rc)
     if lin:
         out["d"] = dff.reshape(bt, N - 1, m)
         out["p"] = pv.reshape(bt, N, n) if all_P else pv.reshape(bt, n)
+    if value:
+        out["s"] = sv.reshape(bt, N) if all_P else sv
+        out["dV"], out["J"] = dVv, Jv
     return out
 
 
 def solve(sol: LQRSolution, solver: DPSolver, prob: LQRProblem) -> LQRSolution:
     """solve!(sol, solver, prob) — dynamic_programming.jl:54-72 (one problem)."""
     all_P = sol.P.ndim == 3
-    out = solve_batch(LQRBatch.of([prob]), solver.dtype, all_P)
+    value = sol.s is not None
+    out = solve_batch(LQRBatch.of([prob]), solver.dtype, all_P, value=value)
     sol.K[...] = out["K"][0]
     sol.X[...] = out["X"][0]
     sol.U[...] = out["U"][0]
     sol.P[...] = out["P"][0]
     sol.info = int(out["info"][0])
-    if prob.q is not None or prob.c is not None or prob.M is not None:
+    if prob.q is not None or prob.c is not None or prob.M is not None or value:
         sol.d = out["d"][0]
         sol.p = out["p"][0]
+    if value:
+        sol.s, sol.dV, sol.J = out["s"][0], out["dV"][0], out["J"][0]
     return sol
 
 
@@ -393,7 +425,7 @@ def abi_to_batch(d: dict) -> LQRBatch:
 
 
 def dp_solve_device(t: dict, N: int, p_mode: int = 0, stream: int | None = None,
-                    out: dict | None = None, layout: int = 0) -> dict:
+                    out: dict | None = None, layout: int = 0, value: bool = False) -> dict:
     """Device-pointer entry point on torch tensors already in ABI layout (flat; layout 1 =
     batch fastest, every input and output).
 
@@ -401,7 +433,10 @@ def dp_solve_device(t: dict, N: int, p_mode: int = 0, stream: int | None = None,
     tensors q, r, qf as well it runs lqrx_dp_solve_linear and also returns d and p; with a
     tensor c too (n·batch, or n·(N−1)·batch with tv_AB) it runs lqrx_dp_solve_affine; with a
     tensor M on top of those (m·n·batch, or m·n·(N−1)·batch with tv_QR) lqrx_dp_solve_cross.
-    Returns dict of output tensors (K, P, X, U, info[, d, p]).  `stream` is a raw hipStream_t
+    value=True (needs M, c, q, r, qf) runs lqrx_dp_solve_value and also returns s (batch, or
+    N·batch with p_mode 1), dV and J (batch); an `out` that holds s but None (or nothing) for dV
+    or J passes NULL for it, and the library skips it.
+    Returns dict of output tensors (K, P, X, U, info[, d, p[, s, dV, J]]).  `stream` is a raw hipStream_t
     (torch.cuda.current_stream().cuda_stream); None = the null stream, synchronous.
     """
     import torch
@@ -424,13 +459,26 @@ def dp_solve_device(t: dict, N: int, p_mode: int = 0, stream: int | None = None,
         raise ValueError("dp_solve_device: c needs q, r, qf (zeros for a problem without cost terms)")
     if t.get("M") is not None and t.get("c") is None:
         raise ValueError("dp_solve_device: M needs c and q, r, qf (zeros where the problem has none)")
+    if value and t.get("M") is None:
+        raise ValueError("dp_solve_device: value=True needs M, c and q, r, qf (zeros where the problem has none)")
     if t.get("q") is not None:
         if "d" not in out:
             out["d"] = torch.empty(bt * (N - 1) * m, dtype=tdt, device=dev)
             out["p"] = torch.empty(bt * n * (N if p_mode else 1), dtype=tdt, device=dev)
         ln = _lib.DpLinear(t["q"].data_ptr(), t["r"].data_ptr(), t["qf"].data_ptr(),
                            out["d"].data_ptr(), out["p"].data_ptr())
-        if t.get("M") is not None:
+        if value:
+            if "s" not in out:
+                out["s"] = torch.empty(bt * (N if p_mode else 1), dtype=tdt, device=dev)
+                out["dV"] = torch.empty(bt, dtype=tdt, device=dev)
+                out["J"] = torch.empty(bt, dtype=tdt, device=dev)
+            opt = lambda k: out[k].data_ptr() if out.get(k) is not None else None   # dV, J: optional
+            vl = _lib.DpValue(out["s"].data_ptr(), opt("dV"), opt("J"))
+            rc = lib.lqrx_dp_solve_value(C.byref(d), p(t["A"]), p(t["B"]), p(t["c"]), p(t["Q"]),
+                                         p(t["R"]), p(t["M"]), p(t["Qf"]), p(t["x0"]), C.byref(ln),
+                                         C.byref(vl), p(out["K"]), p(out["P"]), p(out["X"]),
+                                         p(out["U"]), p(out["info"]), st)
+        elif t.get("M") is not None:
             rc = lib.lqrx_dp_solve_cross(C.byref(d), p(t["A"]), p(t["B"]), p(t["c"]), p(t["Q"]),
                                          p(t["R"]), p(t["M"]), p(t["Qf"]), p(t["x0"]), C.byref(ln),
                                          p(out["K"]), p(out["P"]), p(out["X"]), p(out["U"]),

@@ -49,7 +49,8 @@ extern "C" {
                                    lqrx_dp_solve_affine[_host], lqrx_dp_solve_cross[_host] and
                                    lqrx_dp_solve_value[_host] are additive to ABI 5 (no existing
                                    signature or struct changed, the number stays 5): detect
-                                   them by symbol (dlsym) */
+                                   them by symbol (dlsym); so are lqrx_dp_costates[_host] and
+                                   lqrx_dp_solve_adjoint */
 
 #define LQRX_F64 0
 #define LQRX_F32 1
@@ -287,6 +288,89 @@ int lqrx_dp_solve_value_host(const lqrx_dp_desc *desc, const void *A, const void
                              const void *Qf, const void *x0, const lqrx_dp_linear *lin,
                              const lqrx_dp_value *val, void *K, void *P, void *X, void *U,
                              int32_t *info);
+
+/* ------------------------------------------------------------------------------------
+ * Costates of a DP solve — the multipliers of the dynamics constraints, with the sign
+ * λ_k = ∂V_k/∂x = P_k x_k + p_k (the negative of the KKT path's lam for the same problem): what an
+ * SQP caller needs for its dual residual and merit function and an iLQR caller for the
+ * Hamiltonian.  They come from one backward sweep over the solve's own K, X, U, without P_k:
+ *   λ_N = Qf x_N + qf
+ *   λ_k = Q_k x_k + M_kᵀu_k + q_k + A_kᵀλ_{k+1} − K_kᵀ s_k          k = N−1 … 1
+ *   s_k = R_k u_k + M_k x_k + r_k + B_kᵀλ_{k+1}                      (= 0 at the solution)
+ * s_k is the stationarity condition, so the last term is zero in exact arithmetic and the sweep is
+ * the textbook λ_k = Q_k x_k + M_kᵀu_k + q_k + A_kᵀλ_{k+1}; with it the recursion runs through the
+ * closed loop (A_k − B_kK_k)ᵀ, which the solve made stable.  The textbook form propagates rounding
+ * errors with the open-loop A_kᵀ: at n = 32, m = 16, N = 256 with ρ(A) = 1.14 it is wrong in the
+ * fifth digit in fp64, the form above exact to 3e-15.  The price: a caller needs the solve's K and
+ * the problem's B, R, r to get multipliers, and the sweep reads 2n² + m² + 3nm elements per knot
+ * where the textbook form reads 2n² + nm (1.5 times the bytes at m = n/2).  λ_1 = ∂J/∂x0.
+ *   A, B, Q, R, Qf, K, X, U   the problem and the outputs of the solve (knot strides of desc)
+ *   M, q, r, qf               may be NULL, meaning zero (so the outputs of a plain lqrx_dp_solve
+ *                             have multipliers too); M, q, r follow knot_stride_QR
+ *   lam                       out: n·N·batch, laid out like X (λ_k of trajectory b at [(b·N + k−1)·n])
+ * desc.p_mode is ignored.  Every (n, m ≤ 512, dtype, knot stride) the solve accepts is accepted;
+ * desc.layout = 1 returns LQRX_ERR_UNSUPPORTED (a follow-up).  Error codes follow the argument
+ * position: desc −1, A −2, B −3, Q −4, R −5, Qf −7, K −11, X −12, U −13, lam −14, decided before
+ * the device is touched; batch = 0 returns 0.  Results are the same bits from run to run (no atomics).
+ * Additive to ABI 5: detect by symbol.
+ * ------------------------------------------------------------------------------------ */
+int lqrx_dp_costates(const lqrx_dp_desc *desc, const void *A, const void *B, const void *Q,
+                     const void *R, const void *M, const void *Qf, const void *q, const void *r,
+                     const void *qf, const void *K, const void *X, const void *U, void *lam,
+                     void *stream);
+
+/* host pointers everywhere: H2D, sweep, D2H, synchronous */
+int lqrx_dp_costates_host(const lqrx_dp_desc *desc, const void *A, const void *B, const void *Q,
+                          const void *R, const void *M, const void *Qf, const void *q,
+                          const void *r, const void *qf, const void *K, const void *X,
+                          const void *U, void *lam);
+
+/* ------------------------------------------------------------------------------------
+ * Gradients through the solve (adjoint pass): for a loss ℓ(X, U) of the solution of
+ * lqrx_dp_solve_cross, ∂ℓ/∂(A, B, c, Q, R, M, Qf, x0, q, r, qf) by the implicit-function theorem on
+ * the KKT system.  With gX_k = ∂ℓ/∂x_k (k = 1…N) and gU_k = ∂ℓ/∂u_k (k = 1…N−1), solve the same
+ * problem with q'_k = gX_k (k < N), qf' = gX_N, r'_k = gU_k, c' = 0, x0' = 0; call its solution
+ * X', U' and its costates λ' (the sweep of lqrx_dp_costates on it).  Then
+ *   ∂ℓ/∂A_k = λ'_{k+1} x_kᵀ + λ_{k+1} x'_kᵀ     ∂ℓ/∂B_k = λ'_{k+1} u_kᵀ + λ_{k+1} u'_kᵀ     ∂ℓ/∂c_k = λ'_{k+1}
+ *   ∂ℓ/∂Q_k = ½(x'_k x_kᵀ + x_k x'_kᵀ)          ∂ℓ/∂R_k = ½(u'_k u_kᵀ + u_k u'_kᵀ)          ∂ℓ/∂M_k = u'_k x_kᵀ + u_k x'_kᵀ
+ *   ∂ℓ/∂Qf  = ½(x'_N x_Nᵀ + x_N x'_Nᵀ)          ∂ℓ/∂q_k = x'_k    ∂ℓ/∂r_k = u'_k    ∂ℓ/∂qf = x'_N    ∂ℓ/∂x0 = λ'_1
+ * gQ, gR, gQf are gradients with respect to the symmetric matrix (the solve reads Q, R, Qf as
+ * symmetric).  x'_1 = 0, so gq_1 = 0 and gQ_1 = 0 exactly.
+ *   A, B, Q, R, M, Qf   the forward problem (M required, as in lqrx_dp_solve_cross: a caller
+ *                       without a cross term passes zeros and gM = NULL)
+ *   X, U, lam           the forward solve's outputs and its costates (lqrx_dp_costates)
+ *   grad->gX, gU        in: n·N·batch, m·(N−1)·batch
+ *   grad->g*            out, each optional (NULL: not formed, and costs nothing), shaped like the
+ *                       field: gQ, gR, gM, gq, gr per knot; gA, gB, gc per knot with
+ *                       knot_stride_AB = 1 and summed over the knots, in ascending k, with 0
+ *   info                optional: the adjoint solve's info, equal to the forward one (E does not
+ *                       depend on the linear terms); gradients of a trajectory with info ≠ 0
+ *                       are unspecified
+ * desc.knot_stride_QR must be 1, because gX, gU sit where per-knot q, r go: a stride of 0 returns
+ * LQRX_ERR_UNSUPPORTED (broadcast Q, R, M over the knots and sum gQ, gR, gM over them).
+ * desc.layout = 1 returns LQRX_ERR_UNSUPPORTED (a follow-up).  desc.p_mode is ignored.
+ * The call runs, all on `stream`: a repack of gX into q', qf'; the cross solve (the kernels of
+ * lqrx_dp_solve_cross); the costate sweep on it; the assembly kernels.  Scratch comes from the
+ * library pool and is freed in stream order: per trajectory
+ *   m·n·(N−1) [K'] + 2·n·N [X', λ'] + (n + 2m)(N−1) [q', U', d'] + n·(N−1 or 1) [c'] + n² + 3n
+ * elements (K' dominates: 1.05 MB per fp64 trajectory at n = 32, m = 16, N = 256).  The batch is
+ * not chunked to cap it — split the batch to bound the scratch.
+ * Error codes follow the argument position: desc −1, A −2, B −3, Q −4, R −5, M −6, Qf −7, X −8,
+ * U −9, lam −10, grad or its members gX, gU −11, decided before the device is touched;
+ * batch = 0 returns 0.  Results are the same bits from run to run (no atomics), and an output
+ * has the same bits whichever other outputs are asked for.
+ * There is no _host twin and no _host_devices twin of this entry.  Additive to ABI 5: detect by symbol.
+ * ------------------------------------------------------------------------------------ */
+typedef struct lqrx_dp_grad {
+    const void *gX, *gU;                 /* in: ∂ℓ/∂X (n·N·batch), ∂ℓ/∂U (m·(N−1)·batch)   */
+    void *gA, *gB, *gc;                  /* out, each optional (NULL: not formed)           */
+    void *gQ, *gR, *gM, *gQf, *gx0, *gq, *gr, *gqf;
+} lqrx_dp_grad;
+
+int lqrx_dp_solve_adjoint(const lqrx_dp_desc *desc, const void *A, const void *B, const void *Q,
+                          const void *R, const void *M, const void *Qf, const void *X,
+                          const void *U, const void *lam, const lqrx_dp_grad *grad,
+                          int32_t *info, void *stream);
 
 /* ------------------------------------------------------------------------------------
  * KKT path: one inner solve of CholeskySolver._solve!(solver)

@@ -294,6 +294,34 @@ function solve_linear!(sol::LQRSolution{T}, d::Array{T,3}, p::Array{T}, solver::
     end
     return check(rc)
 end
+
+"""
+    costates!(lam, sol, solver, prob; M = nothing, q = nothing, r = nothing, qf = nothing)
+
+Costates λ_k = P_k x_k + p_k of a solve that has run (`sol` holds its K, X, U), the multipliers of
+the dynamics constraints (the negative of the KKT path's lam): `lam` is n×N×batch, laid out like
+X.  lqrx_dp_costates_host — one closed-loop backward sweep; time-invariant fields, layout 0.  The
+keywords are the problem's cross term and linear cost terms (m×n×batch, n×batch, m×batch, n×batch);
+`nothing` is passed as NULL and means zero.  Additive to ABI 5, bound by symbol.  The adjoint pass
+(lqrx_dp_solve_adjoint) works on device pointers only and is not bound here.
+"""
+function costates!(lam::Array{T,3}, sol::LQRSolution{T}, solver::DPSolver{T}, prob::LQRBatch{T};
+                   M::Union{Nothing,Array{T,3}} = nothing, q::Union{Nothing,Matrix{T}} = nothing,
+                   r::Union{Nothing,Matrix{T}} = nothing, qf::Union{Nothing,Matrix{T}} = nothing) where T
+    n, m, N = solver.n, solver.m, solver.N
+    batch = size(prob.A, 3)
+    size(lam) == (n, N, batch) || throw(ArgumentError("lam must be n×N×batch"))
+    desc = Ref(DpDesc(n, m, N, dtypecode(T), batch, 0, 0, 0, 0))
+    opt(a) = a === nothing ? Ptr{T}(C_NULL) : pointer(a)
+    GC.@preserve prob sol lam M q r qf begin
+        rc = ccall((:lqrx_dp_costates_host, liblqrx), Cint,
+                   (Ref{DpDesc}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T},
+                    Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}),
+                   desc, prob.A, prob.B, prob.Q, prob.R, opt(M), prob.Qf, opt(q), opt(r), opt(qf),
+                   sol.Kdata, sol.Xdata, sol.Udata, lam)
+    end
+    return check(rc)
+end
 # ---- KKT: lqrx_kkt_desc ----
 struct KktDesc
     N::Int32; dtype::Int32
@@ -407,7 +435,7 @@ function sqp_solve!(Z::Matrix{Float64}, lam::Matrix{Float64}, iters::Vector{Int3
 end
 
 export LQRProblem, LQRSolution, LQRBatch, DPSolver, solve!, solve_linear!, kkt_solve!, ls_solve!,
-       compute_gain!, compute_ctg!,
+       compute_gain!, compute_ctg!, costates!,
        sqp_solve!, num_vars
 
 end # module

@@ -620,6 +620,189 @@ int lqrx_dp_solve_value_host(const lqrx_dp_desc *d, const void *A, const void *B
                               true);
 }
 
+} // extern "C"
+
+namespace {
+// Descriptor checks shared by lqrx_dp_costates[_host] and lqrx_dp_solve_adjoint: p_mode is
+// ignored, layout 1 is a stated follow-up
+int validate_dp_adjoint(const lqrx_dp_desc *d, const char *entry)
+{
+    if (!d) return set_err(-1, "desc is NULL");
+    lqrx_dp_desc d0 = *d;
+    d0.p_mode = 0;
+    int st = validate_dp(&d0);
+    if (st) return st;
+    if (d->layout != 0)
+        return set_err(LQRX_ERR_UNSUPPORTED, "%s: desc.layout = 1 is not supported (layout 0 only)", entry);
+    return 0;
+}
+
+// The arguments of lqrx_dp_costates[_host] behind desc, in order: A 2, B 3, Q 4, R 5, M 6, Qf 7,
+// q 8, r 9, qf 10, K 11, X 12, U 13, lam 14; M, q, r, qf may be NULL (zero)
+struct CostatePtrs {
+    const void *A, *B, *Q, *R, *M, *Qf, *q, *r, *qf, *K, *X, *U;
+    void *lam;
+};
+
+int check_costate_ptrs(const CostatePtrs &c)
+{
+    const void *p[13] = {c.A, c.B, c.Q, c.R, c.M, c.Qf, c.q, c.r, c.qf, c.K, c.X, c.U, c.lam};
+    static const char *nm[13] = {"A", "B", "Q", "R", "M", "Qf", "q", "r", "qf", "K", "X", "U", "lam"};
+    static const bool optional[13] = {false, false, false, false, true, false, true, true, true, false, false, false, false};
+    for (int i = 0; i < 13; ++i)
+        if (!p[i] && !optional[i]) return set_err(-(i + 2), "pointer %d (%s) is NULL", i + 2, nm[i]);
+    return 0;
+}
+
+lqrx::DpCostateArgs costate_args(const lqrx_dp_desc *d, const CostatePtrs &c)
+{
+    lqrx::DpCostateArgs a{};
+    a.A = c.A; a.B = c.B; a.Q = c.Q; a.R = c.R; a.M = c.M; a.Qf = c.Qf; a.q = c.q; a.r = c.r; a.qf = c.qf;
+    a.K = c.K; a.X = c.X; a.U = c.U; a.lam = c.lam;
+    a.n = d->n; a.m = d->m; a.N = d->N; a.dtype = d->dtype;
+    a.tv_AB = (int)d->knot_stride_AB; a.tv_QR = (int)d->knot_stride_QR;
+    a.batch = d->batch;
+    return a;
+}
+} // namespace
+
+extern "C" {
+
+// costates λ_k = P_k x_k + p_k of a solve, by the closed-loop backward sweep on its K, X, U (see lqrx.h)
+int lqrx_dp_costates(const lqrx_dp_desc *d, const void *A, const void *B, const void *Q, const void *R,
+                     const void *M, const void *Qf, const void *q, const void *r, const void *qf, const void *K,
+                     const void *X, const void *U, void *lam, void *stream)
+{
+    int st = validate_dp_adjoint(d, "lqrx_dp_costates");
+    if (st) return st;
+    if (d->batch == 0) return 0;
+    const CostatePtrs c{A, B, Q, R, M, Qf, q, r, qf, K, X, U, lam};
+    if ((st = check_costate_ptrs(c))) return st;
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = lqrx::dp_costate_launch(costate_args(d, c), s);
+    if (e == hipErrorNotSupported) return set_err(LQRX_ERR_UNSUPPORTED, "no costate kernel for n=%d m=%d", d->n, d->m);
+    if (e != hipSuccess) return hip_err(e, "costate kernel launch");
+    if (stream == nullptr && (e = hipStreamSynchronize(nullptr)) != hipSuccess) return hip_err(e, "costate kernel");
+    return 0;
+}
+
+int lqrx_dp_costates_host(const lqrx_dp_desc *d, const void *A, const void *B, const void *Q, const void *R,
+                          const void *M, const void *Qf, const void *q, const void *r, const void *qf,
+                          const void *K, const void *X, const void *U, void *lam)
+{
+    int st = validate_dp_adjoint(d, "lqrx_dp_costates_host");
+    if (st) return st;
+    if (d->batch == 0) return 0;
+    if ((st = check_costate_ptrs(CostatePtrs{A, B, Q, R, M, Qf, q, r, qf, K, X, U, lam}))) return st;
+    const size_t es = dsize(d->dtype), bt = (size_t)d->batch, n = d->n, m = d->m, N = d->N;
+    const size_t kAB = d->knot_stride_AB ? N - 1 : 1, kQR = d->knot_stride_QR ? N - 1 : 1;
+    const void *hin[12] = {A, B, Q, R, M, Qf, q, r, qf, K, X, U};
+    const size_t szin[12] = {n * n * kAB, n * m * kAB, n * n * kQR, m * m * kQR, m * n * kQR, n * n,
+                             n * kQR, m * kQR, n, m * n * (N - 1), n * N, m * (N - 1)};
+    DevBuf din[12], dlam;
+    for (int i = 0; i < 12; ++i) {
+        if (!hin[i]) continue;   // M, q, r, qf: NULL means zero
+        if ((st = dev_alloc(din[i], szin[i] * es * bt, "hipMalloc input"))) return st;
+        const hipError_t e = hipMemcpy(din[i].p, hin[i], szin[i] * es * bt, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return hip_err(e, "H2D");
+    }
+    if ((st = dev_alloc(dlam, n * N * es * bt, "hipMalloc lam"))) return st;
+    st = lqrx_dp_costates(d, din[0].p, din[1].p, din[2].p, din[3].p, din[4].p, din[5].p, din[6].p, din[7].p,
+                          din[8].p, din[9].p, din[10].p, din[11].p, dlam.p, nullptr);
+    if (st < 0) return st;
+    const hipError_t e = hipMemcpy(lam, dlam.p, n * N * es * bt, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_err(e, "D2H lam");
+    return st;
+}
+
+// Gradients of a loss ℓ(X, U) through the solve: one more cross solve with ∂ℓ/∂X, ∂ℓ/∂U as the
+// linear cost terms (x0' = 0, c' = 0), its costates, and the rank-2 assembly (see lqrx.h)
+int lqrx_dp_solve_adjoint(const lqrx_dp_desc *d, const void *A, const void *B, const void *Q, const void *R,
+                          const void *M, const void *Qf, const void *X, const void *U, const void *lam,
+                          const lqrx_dp_grad *grad, int32_t *info, void *stream)
+{
+    int st = validate_dp_adjoint(d, "lqrx_dp_solve_adjoint");
+    if (st) return st;
+    if (d->knot_stride_QR != 1)
+        return set_err(LQRX_ERR_UNSUPPORTED, "lqrx_dp_solve_adjoint: desc.knot_stride_QR must be 1 (dl/dX and dl/dU "
+                                             "take the place of per-knot q, r): broadcast Q, R, M over the knots");
+    if (d->batch == 0) return 0;
+    const void *in[9] = {A, B, Q, R, M, Qf, X, U, lam};
+    static const char *inm[9] = {"A", "B", "Q", "R", "M", "Qf", "X", "U", "lam"};
+    for (int i = 0; i < 9; ++i)
+        if (!in[i]) return set_err(-(i + 2), "input pointer %d (%s) is NULL", i + 2, inm[i]);
+    if (!grad) return set_err(-11, "grad is NULL");
+    if (!grad->gX || !grad->gU) return set_err(-11, "grad->%s is NULL", grad->gX ? "gU" : "gX");
+
+    const size_t es = dsize(d->dtype), bt = (size_t)d->batch, n = d->n, m = d->m, N = d->N;
+    const int tvAB = (int)d->knot_stride_AB;
+    // scratch of the adjoint solve, elements per trajectory: q' n(N−1), qf' n, c' n(N−1 | 1), x0' n,
+    // K' mn(N−1), P'_1 n², X' nN, U' m(N−1), d' m(N−1), p'_1 n, λ' nN — and info' when the caller passes none
+    const size_t cnt[11] = {n * (N - 1), n, n * (tvAB ? N - 1 : 1), n, m * n * (N - 1), n * n,
+                            n * N, m * (N - 1), m * (N - 1), n, n * N};
+    size_t off[12], total = 0;
+    for (int i = 0; i < 11; ++i) {
+        off[i] = total;
+        total += (cnt[i] * bt * es + 255) & ~(size_t)255;
+    }
+    off[11] = total;
+    if (!info) total += (4 * bt + 255) & ~(size_t)255;
+    hipStream_t s = (hipStream_t)stream;
+    void *blk = nullptr;
+    hipError_t e = lqrx::scratch_alloc(&blk, total, s);
+    if (e != hipSuccess) return hip_err(e, "adjoint scratch");
+    char *b = (char *)blk;
+    void *qa = b + off[0], *qfa = b + off[1], *ca = b + off[2], *x0a = b + off[3], *Ka = b + off[4];
+    void *Pa = b + off[5], *Xa = b + off[6], *Ua = b + off[7], *da = b + off[8], *pa = b + off[9], *lama = b + off[10];
+    int32_t *infoa = info ? info : (int32_t *)(b + off[11]);
+    const char *what = "adjoint pack";
+    e = lqrx::dp_adjoint_pack_launch(grad->gX, qa, qfa, (int)n, (int)N, d->batch, d->dtype, s);
+    if (e == hipSuccess) {
+        what = "adjoint zero fill";   // c' and x0' are adjacent in the block
+        e = hipMemsetAsync(ca, 0, off[4] - off[2], s);
+    }
+    if (e == hipSuccess) {
+        what = "adjoint solve";
+        lqrx::DpArgs a{};
+        a.lin = a.aff = a.cross = 1;
+        a.A = A; a.B = B; a.Q = Q; a.R = R; a.Qf = Qf; a.x0 = x0a; a.c = ca; a.M = M;
+        a.q = qa; a.r = grad->gU; a.qf = qfa; a.d = da; a.p = pa;
+        a.K = Ka; a.P = Pa; a.X = Xa; a.U = Ua; a.info = infoa;
+        a.n = d->n; a.m = d->m; a.N = d->N; a.dtype = d->dtype; a.p_all = 0; a.batch = d->batch;
+        a.tv_AB = tvAB; a.tv_QR = 1; a.layout = 0;
+        e = lqrx::dp_launch(a, s);
+    }
+    if (e == hipSuccess) {
+        what = "adjoint costates";
+        e = lqrx::dp_costate_launch(costate_args(d, CostatePtrs{A, B, Q, R, M, Qf, qa, grad->gU, qfa, Ka, Xa, Ua, lama}), s);
+    }
+    if (e == hipSuccess) {
+        what = "adjoint assembly";
+        lqrx::DpGradArgs g{};
+        g.X = X; g.U = U; g.lam = lam; g.Xa = Xa; g.Ua = Ua; g.lama = lama;
+        g.gA = grad->gA; g.gB = grad->gB; g.gc = grad->gc; g.gQ = grad->gQ; g.gR = grad->gR; g.gM = grad->gM;
+        g.gQf = grad->gQf; g.gx0 = grad->gx0; g.gq = grad->gq; g.gr = grad->gr; g.gqf = grad->gqf;
+        g.n = d->n; g.m = d->m; g.N = d->N; g.dtype = d->dtype; g.tv_AB = tvAB; g.batch = d->batch;
+        e = lqrx::dp_grad_launch(g, s);
+    }
+    int any = 0;
+    if (e == hipSuccess && stream == nullptr) {
+        what = "adjoint kernels";
+        e = hipStreamSynchronize(nullptr);
+        if (e == hipSuccess && info) {
+            std::vector<int32_t> h(bt);
+            e = hipMemcpy(h.data(), info, bt * 4, hipMemcpyDeviceToHost);
+            for (int32_t v : h)
+                if (v) any = 1;
+        }
+    }
+    const hipError_t ef = lqrx::scratch_free(blk, s);
+    if (e == hipErrorNotSupported) return set_err(LQRX_ERR_UNSUPPORTED, "no kernel for n=%d m=%d", d->n, d->m);
+    if (e != hipSuccess) return hip_err(e, what);
+    if (ef != hipSuccess) return hip_err(ef, "adjoint scratch free");
+    return any;
+}
+
 
 // ------------------------------------------------------------------ KKT
 namespace {

@@ -61,6 +61,36 @@ bool dp_lane_supported(int n, int m);
 hipError_t dp_big_launch(const DpArgs &a, hipStream_t s);
 bool dp_big_supported(int n, int m);
 
+// ---- costates and the adjoint pass (lqrx_dp_adjoint.hip), layout 0 only ----
+// λ_N = Qf x_N + qf,  λ_k = Q_k x_k + M_kᵀu_k + q_k + A_kᵀλ_{k+1} − K_kᵀ(R_k u_k + M_k x_k + r_k + B_kᵀλ_{k+1})
+// (the bracket is the stationarity condition, zero at the solution: the closed-loop, stable form
+// of the sweep): lam laid out like X.  M, q, r, qf may be null (zero).  Q, R, M, q, r follow tv_QR,
+// A, B follow tv_AB; K is the solve's gain, per knot.
+struct DpCostateArgs {
+    const void *A, *B, *Q, *R, *M, *Qf, *q, *r, *qf, *K, *X, *U;
+    void *lam;
+    int n, m, N;
+    int dtype; // 0 f64, 1 f32
+    int tv_AB, tv_QR;
+    int64_t batch;
+};
+hipError_t dp_costate_launch(const DpCostateArgs &a, hipStream_t s);
+// gX (n·N per trajectory) → q' (n·(N−1) per trajectory), qf' (n per trajectory)
+hipError_t dp_adjoint_pack_launch(const void *gX, void *q, void *qf, int n, int N, int64_t batch, int dtype,
+                                  hipStream_t s);
+// Rank-2 assembly of the gradients from the forward (X, U, lam) and adjoint (Xa, Ua, lama)
+// trajectories; every output may be null (not formed).  gA, gB, gc are per knot with tv_AB, else
+// summed over the knots in ascending k; gQ, gR, gM, gq, gr are per knot.
+struct DpGradArgs {
+    const void *X, *U, *lam, *Xa, *Ua, *lama;
+    void *gA, *gB, *gc, *gQ, *gR, *gM, *gQf, *gx0, *gq, *gr, *gqf;
+    int n, m, N;
+    int dtype;
+    int tv_AB;
+    int64_t batch;
+};
+hipError_t dp_grad_launch(const DpGradArgs &a, hipStream_t s);
+
 struct KktArgs {
     const double *Y, *y, *H, *g; // device, packed per trajectory
     double *dz, *lam;

@@ -40,6 +40,13 @@ class DpValue(C.Structure):
     _fields_ = [("s", C.c_void_p), ("dV", C.c_void_p), ("J", C.c_void_p)]
 
 
+class DpGrad(C.Structure):
+    """Mirror of ``lqrx_dp_grad`` (adjoint pass: gX, gU in; every gradient out and optional)."""
+
+    _fields_ = [(k, C.c_void_p) for k in ("gX", "gU", "gA", "gB", "gc", "gQ", "gR", "gM", "gQf",
+                                          "gx0", "gq", "gr", "gqf")]
+
+
 class KktDesc(C.Structure):
     """Mirror of ``lqrx_kkt_desc``."""
 
@@ -108,6 +115,10 @@ _SIGS = {
                             + [C.POINTER(DpValue)] + [_VP] * 4 + [_VP, _VP]),
     "lqrx_dp_solve_value_host": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 8
                                  + [C.POINTER(DpLinear)] + [C.POINTER(DpValue)] + [_VP] * 5),
+    "lqrx_dp_costates": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 13 + [_VP]),
+    "lqrx_dp_costates_host": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 13),
+    "lqrx_dp_solve_adjoint": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 9 + [C.POINTER(DpGrad)]
+                              + [_VP, _VP]),
     "lqrx_dp_solve_host_devices": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 10 + [_VP, _VP, C.c_int32]),
     "lqrx_dp_solve_linear_host_devices": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 6 + [C.POINTER(DpLinear)]
                                           + [_VP] * 5 + [_VP, C.c_int32]),

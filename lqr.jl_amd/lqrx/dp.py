@@ -113,16 +113,19 @@ class LQRSolution:
     s: np.ndarray | None = None
     dV: np.ndarray | None = None
     J: np.ndarray | None = None
+    # costates λ_k = P_k x_k + p_k, (N, n) (of(…, costates=True)): the multipliers of the dynamics
+    lam: np.ndarray | None = None
 
     @classmethod
-    def of(cls, prob: LQRProblem, all_P: bool = False, value: bool = False):
+    def of(cls, prob: LQRProblem, all_P: bool = False, value: bool = False, costates: bool = False):
         n, m, N = prob.size()
         lin = prob.q is not None or prob.c is not None or prob.M is not None or value
         val = dict(s=np.zeros(N) if all_P else np.zeros(()), dV=np.zeros(()), J=np.zeros(())) if value else {}
         return cls(np.zeros((N - 1, m, n)), np.zeros((N, n)), np.zeros((N - 1, m)),
                    np.zeros((N, n, n)) if all_P else np.zeros((n, n)),
                    d=np.zeros((N - 1, m)) if lin else None,
-                   p=(np.zeros((N, n)) if all_P else np.zeros(n)) if lin else None, **val)
+                   p=(np.zeros((N, n)) if all_P else np.zeros(n)) if lin else None,
+                   lam=np.zeros((N, n)) if costates else None, **val)
 
 
 @dataclass
@@ -212,7 +215,7 @@ def _devices(devices):
 
 
 def solve_batch(b: LQRBatch, dtype: int = _lib.F64, all_P: bool = False, layout: int = 0,
-                devices=None, value: bool = False):
+                devices=None, value: bool = False, costates: bool = False):
     """Batched solve! through lqrx_dp_solve_host.  Returns dict of logical arrays
     K (batch, N-1, m, n), P (batch, n, n) or (batch, N, n, n), X (batch, N, n),
     U (batch, N-1, m), info (batch,), and the ABI return code.  layout = 1 hands the
@@ -224,7 +227,9 @@ def solve_batch(b: LQRBatch, dtype: int = _lib.F64, all_P: bool = False, layout:
     lqrx_dp_solve_cross_host: a missing c is zeros as well; no devices= form either.  With
     value=True the call is lqrx_dp_solve_value_host: missing c, M, q, r, qf are zeros, and the
     result gains s ((batch,) s_1, or (batch, N) every s_k with all_P), dV and J ((batch,)); no
-    devices= form."""
+    devices= form.  With costates=True the result gains lam (batch, N, n), the costates
+    λ_k = P_k x_k + p_k of the solution, by one more call (lqrx_dp_costates_host, layout 0) on the
+    K, X, U just returned."""
     n, m, N = b.size()
     bt = b.batch
     tvAB, tvQR = b.time_varying()
@@ -260,6 +265,7 @@ def solve_batch(b: LQRBatch, dtype: int = _lib.F64, all_P: bool = False, layout:
                      qf=b.qf if b.qf is not None else zeros(bt, n), c=b.c, M=b.M)
     lib = _lib.load()
     ins = [to_abi(np.asarray(x, dtype=npdt)) for x in (b.A, b.B, b.Q, b.R, b.Qf)]
+    ins0 = ins   # layout 0, for the costate sweep
     x0 = np.ascontiguousarray(np.asarray(b.x0, dtype=npdt))
     if layout == 1:
         ins = [to_soa(a, bt) for a in ins]
@@ -333,6 +339,18 @@ def solve_batch(b: LQRBatch, dtype: int = _lib.F64, all_P: bool = False, layout:
     if value:
         out["s"] = sv.reshape(bt, N) if all_P else sv
         out["dV"], out["J"] = dVv, Jv
+    if costates:   # λ_k from the K, X, U just returned; absent M, q, r, qf are NULL (zero)
+        flat = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a, dtype=npdt)).reshape(-1)
+        Mc = to_abi(np.asarray(b.M, dtype=npdt)).reshape(-1) if cross else None
+        qc, rc_, qfc = flat(b.q), flat(b.r), flat(b.qf)
+        Kc = to_abi(out["K"]).reshape(-1)
+        Xc, Uc = flat(out["X"]), flat(out["U"])
+        lam = np.zeros(bt * N * n, npdt)
+        d0 = _lib.DpDesc(n, m, N, dtype, bt, 0, 0, tvAB, tvQR)
+        op = lambda a: None if a is None else _ptr(a)
+        _lib.check(lib.lqrx_dp_costates_host(C.byref(d0), *[_ptr(a) for a in ins0[:4]], op(Mc), _ptr(ins0[4]),
+                                             op(qc), op(rc_), op(qfc), _ptr(Kc), _ptr(Xc), _ptr(Uc), _ptr(lam)))
+        out["lam"] = lam.reshape(bt, N, n)
     return out
 
 
@@ -340,7 +358,7 @@ def solve(sol: LQRSolution, solver: DPSolver, prob: LQRProblem) -> LQRSolution:
     """solve!(sol, solver, prob) — dynamic_programming.jl:54-72 (one problem)."""
     all_P = sol.P.ndim == 3
     value = sol.s is not None
-    out = solve_batch(LQRBatch.of([prob]), solver.dtype, all_P, value=value)
+    out = solve_batch(LQRBatch.of([prob]), solver.dtype, all_P, value=value, costates=sol.lam is not None)
     sol.K[...] = out["K"][0]
     sol.X[...] = out["X"][0]
     sol.U[...] = out["U"][0]
@@ -351,6 +369,8 @@ def solve(sol: LQRSolution, solver: DPSolver, prob: LQRProblem) -> LQRSolution:
         sol.p = out["p"][0]
     if value:
         sol.s, sol.dV, sol.J = out["s"][0], out["dV"][0], out["J"][0]
+    if sol.lam is not None:
+        sol.lam = out["lam"][0]
     return sol
 
 
@@ -425,7 +445,8 @@ def abi_to_batch(d: dict) -> LQRBatch:
 
 
 def dp_solve_device(t: dict, N: int, p_mode: int = 0, stream: int | None = None,
-                    out: dict | None = None, layout: int = 0, value: bool = False) -> dict:
+                    out: dict | None = None, layout: int = 0, value: bool = False,
+                    costates: bool = False) -> dict:
     """Device-pointer entry point on torch tensors already in ABI layout (flat; layout 1 =
     batch fastest, every input and output).
 
@@ -436,6 +457,8 @@ def dp_solve_device(t: dict, N: int, p_mode: int = 0, stream: int | None = None,
     value=True (needs M, c, q, r, qf) runs lqrx_dp_solve_value and also returns s (batch, or
     N·batch with p_mode 1), dV and J (batch); an `out` that holds s but None (or nothing) for dV
     or J passes NULL for it, and the library skips it.
+    costates=True (layout 0) also returns lam (n·N·batch, laid out like X), the costates
+    λ_k = P_k x_k + p_k, by lqrx_dp_costates on the same stream; absent M, q, r, qf are NULL (zero).
     Returns dict of output tensors (K, P, X, U, info[, d, p[, s, dV, J]]).  `stream` is a raw hipStream_t
     (torch.cuda.current_stream().cuda_stream); None = the null stream, synchronous.
     """
@@ -496,5 +519,12 @@ def dp_solve_device(t: dict, N: int, p_mode: int = 0, stream: int | None = None,
                                p(t["x0"]), p(out["K"]), p(out["P"]), p(out["X"]), p(out["U"]),
                                p(out["info"]), st)
     _lib.check(rc)
+    if costates:
+        if out.get("lam") is None:
+            out["lam"] = torch.empty(bt * N * n, dtype=tdt, device=dev)
+        opt = lambda k: p(t[k]) if t.get(k) is not None else None
+        _lib.check(lib.lqrx_dp_costates(C.byref(d), p(t["A"]), p(t["B"]), p(t["Q"]), p(t["R"]), opt("M"),
+                                        p(t["Qf"]), opt("q"), opt("r"), opt("qf"), p(out["K"]), p(out["X"]),
+                                        p(out["U"]), p(out["lam"]), st))
     out["rc"] = rc
     return out

@@ -11,8 +11,10 @@
 #include "../../include/lqrx.h"
 
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
+#include <string>
 #include <vector>
 
 static int fails = 0;
@@ -30,6 +32,96 @@ static void dubins(int N, std::vector<int32_t> &n1, std::vector<int32_t> &p, std
 {
     n1.assign(N, 3); p.assign(N, 0); n2.assign(N, 3); w.assign(N, 5);
     n1[0] = 0; p[0] = 3; p[N - 1] = 3; n2[N - 1] = 0; w[N - 1] = 3;
+}
+
+// ---- NULL sweep of the DP solve entries (plain, linear, affine, cross, value; device and _host) ----
+// One set of pointers by name; each entry's argument order behind desc as in include/lqrx.h.
+struct DpSlots {
+    const void *A, *B, *c, *Q, *R, *M, *Qf, *x0;
+    lqrx_dp_linear lin;
+    lqrx_dp_value val;
+    void *K, *P, *X, *U;
+    bool no_lin, no_val;
+};
+static const char *const dp_order[5] = {"A B Q R Qf x0 K P X U", "A B Q R Qf x0 lin K P X U", "A B c Q R Qf x0 lin K P X U",
+                                        "A B c Q R M Qf x0 lin K P X U", "A B c Q R M Qf x0 lin val K P X U"};
+static const struct { const char *name; size_t off; } dp_slot[] = {
+    {"A", offsetof(DpSlots, A)}, {"B", offsetof(DpSlots, B)}, {"c", offsetof(DpSlots, c)}, {"Q", offsetof(DpSlots, Q)},
+    {"R", offsetof(DpSlots, R)}, {"M", offsetof(DpSlots, M)}, {"Qf", offsetof(DpSlots, Qf)}, {"x0", offsetof(DpSlots, x0)},
+    {"K", offsetof(DpSlots, K)}, {"P", offsetof(DpSlots, P)}, {"X", offsetof(DpSlots, X)}, {"U", offsetof(DpSlots, U)},
+    {"lin->q", offsetof(DpSlots, lin.q)}, {"lin->r", offsetof(DpSlots, lin.r)}, {"lin->qf", offsetof(DpSlots, lin.qf)},
+    {"lin->d", offsetof(DpSlots, lin.d)}, {"lin->p", offsetof(DpSlots, lin.p)}, {"val->s", offsetof(DpSlots, val.s)},
+    {"val->dV", offsetof(DpSlots, val.dV)}, {"val->J", offsetof(DpSlots, val.J)}};
+
+static DpSlots dp_without(DpSlots s, const std::string &name)
+{
+    if (name == "lin") s.no_lin = true;
+    if (name == "val") s.no_val = true;
+    for (const auto &e : dp_slot)
+        if (name == e.name) std::memset(reinterpret_cast<char *>(&s) + e.off, 0, sizeof(void *));
+    return s;
+}
+
+static int dp_call(int kind, bool host, const lqrx_dp_desc *d, const DpSlots &s, int32_t *info)
+{
+    const lqrx_dp_linear *lin = s.no_lin ? nullptr : &s.lin;
+    const lqrx_dp_value *val = s.no_val ? nullptr : &s.val;
+    switch (kind) {
+    case 0: return host ? lqrx_dp_solve_host(d, s.A, s.B, s.Q, s.R, s.Qf, s.x0, s.K, s.P, s.X, s.U, info)
+                        : lqrx_dp_solve(d, s.A, s.B, s.Q, s.R, s.Qf, s.x0, s.K, s.P, s.X, s.U, info, nullptr);
+    case 1: return host ? lqrx_dp_solve_linear_host(d, s.A, s.B, s.Q, s.R, s.Qf, s.x0, lin, s.K, s.P, s.X, s.U, info)
+                        : lqrx_dp_solve_linear(d, s.A, s.B, s.Q, s.R, s.Qf, s.x0, lin, s.K, s.P, s.X, s.U, info, nullptr);
+    case 2: return host ? lqrx_dp_solve_affine_host(d, s.A, s.B, s.c, s.Q, s.R, s.Qf, s.x0, lin, s.K, s.P, s.X, s.U, info)
+                        : lqrx_dp_solve_affine(d, s.A, s.B, s.c, s.Q, s.R, s.Qf, s.x0, lin, s.K, s.P, s.X, s.U, info, nullptr);
+    case 3: return host ? lqrx_dp_solve_cross_host(d, s.A, s.B, s.c, s.Q, s.R, s.M, s.Qf, s.x0, lin, s.K, s.P, s.X, s.U, info)
+                        : lqrx_dp_solve_cross(d, s.A, s.B, s.c, s.Q, s.R, s.M, s.Qf, s.x0, lin, s.K, s.P, s.X, s.U, info, nullptr);
+    default: return host ? lqrx_dp_solve_value_host(d, s.A, s.B, s.c, s.Q, s.R, s.M, s.Qf, s.x0, lin, val, s.K, s.P, s.X, s.U, info)
+                         : lqrx_dp_solve_value(d, s.A, s.B, s.c, s.Q, s.R, s.M, s.Qf, s.x0, lin, val, s.K, s.P, s.X, s.U, info, nullptr);
+    }
+}
+
+// Every pointer NULL in turn, and each member of lin and val: minus the argument's position, with
+// the argument's name in the text, decided before any device call (so also with no device — the
+// plain and linear _host entries included).  val->dV and val->J may be NULL.
+static void dp_null_sweep(double *buf, int32_t *info)
+{
+    lqrx_dp_desc d{};
+    d.n = 8; d.m = 4; d.N = 10; d.dtype = LQRX_F64; d.batch = 4;
+    const DpSlots full{buf, buf, buf, buf, buf, buf, buf, buf, {buf, buf, buf, buf, buf}, {buf, buf, buf},
+                       buf, buf, buf, buf, false, false};
+    for (int kind = 0; kind < 5; ++kind)
+        for (int host = 0; host < 2; ++host) {
+            std::vector<std::string> order;
+            for (const char *p = dp_order[kind]; *p;) {
+                const char *e = std::strchr(p, ' ');
+                order.emplace_back(p, e ? e : p + std::strlen(p));
+                p = e ? e + 1 : p + std::strlen(p);
+            }
+            int posU = 0;
+            for (size_t i = 0; i < order.size(); ++i) {
+                const int pos = (int)i + 2;              // desc is argument 1
+                std::vector<std::string> names{order[i]};
+                if (order[i] == "lin") names.insert(names.end(), {"lin->q", "lin->r", "lin->qf", "lin->d", "lin->p"});
+                if (order[i] == "val") names.push_back("val->s");
+                if (order[i] == "U") posU = pos;
+                for (const std::string &nm : names) {
+                    const int rc = dp_call(kind, host, &d, dp_without(full, nm), info);
+                    if (rc != -pos || !std::strstr(lqrx_last_error(), nm.c_str())) {
+                        std::fprintf(stderr, "NULL sweep: kind %d host %d %s NULL: got %d (%s), expected %d\n", kind, host,
+                                     nm.c_str(), rc, lqrx_last_error(), -pos);
+                        ++fails;
+                    }
+                }
+            }
+            if (kind == 4) CHECK(dp_call(kind, host, &d, dp_without(dp_without(dp_without(full, "val->dV"), "val->J"), "U"), info) == -posU);
+            CHECK(dp_call(kind, host, nullptr, full, info) == -1);
+            lqrx_dp_desc bad = d;
+            bad.n = 0;                                   // the descriptor comes first, lin == NULL or not
+            CHECK(dp_call(kind, host, &bad, dp_without(full, "lin"), info) == -1);
+            bad = d;
+            bad.batch = 0;                               // empty batch: a no-op whatever the pointers
+            CHECK(dp_call(kind, host, &bad, DpSlots{}, info) == 0);
+        }
 }
 
 int main()
@@ -68,6 +160,7 @@ int main()
         ln.qf = dummy;
         CHECK(lqrx_dp_solve_linear(&d, dummy, dummy, dummy, dummy, dummy, dummy, &ln, dummy, nullptr, dummy, dummy, info, nullptr) == -10);
     }
+    dp_null_sweep(dummy, info);
     b = d; b.batch = 0;                                          // empty batch: nothing to do
     CHECK(lqrx_dp_solve(&b, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == 0);
     if (!have_gpu) {                                             // valid call, no device: clean failure

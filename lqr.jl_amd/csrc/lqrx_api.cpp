@@ -145,52 +145,188 @@ hipError_t scratch_trim(int device, size_t keep)
 } // namespace lqrx
 
 namespace {
+// ---- the DP solve entries: one table of a call's buffers ----
+// The entry kinds nest: each adds arguments to the one before it (lin; c; M; val).
+enum DpKind { DP_PLAIN, DP_LINEAR, DP_AFFINE, DP_CROSS, DP_VALUE };
+
+// the caller's pointers, whatever the entry's argument order
+struct DpPtrs {
+    const void *A, *B, *c, *Q, *R, *M, *Qf, *x0;
+    const lqrx_dp_linear *lin;
+    const lqrx_dp_value *val;
+    void *K, *P, *X, *U;
+    int32_t *info;
+};
+
+struct DpRow {
+    const char *name;
+    void *ptr;       // the caller's buffer, or its device / layout-0 twin in a staged copy of the table
+    size_t field;    // offset of the DpArgs pointer it feeds (kNoField: val->J, or a NULL lin / val)
+    int64_t elems;   // elements per trajectory
+    int arg;         // argument number in the entry that was called (a member of lin, val: the struct's)
+    bool out, optional;
+};
+constexpr size_t kNoField = ~(size_t)0;
+#define DPF(f) offsetof(lqrx::DpArgs, f)
+
+// The rows stand in the called entry's argument order, so a row's argument number is its position
+// (desc is 1; lin and val take one number each, which their members share).  info, optional and
+// int32, is not a row.
+struct DpTable {
+    enum { kIn = 0, kOut = 1, kOptional = 2, kMember = 4, kMaxRows = 20 };
+    DpKind kind;
+    DpRow row[kMaxRows];
+    int nrows = 0, narg = 1, iJ = -1;
+
+    void add(const char *name, const void *ptr, size_t field, int64_t elems, int flags = kIn)
+    {
+        if (!(flags & kMember)) ++narg;
+        row[nrows++] = DpRow{name, const_cast<void *>(ptr), field, elems, narg, (flags & kOut) != 0,
+                             (flags & kOptional) != 0};
+    }
+    // a struct argument: its members follow when it is there, else one NULL row reports it
+    bool open(const char *name, const void *st)
+    {
+        ++narg;
+        if (!st) add(name, nullptr, kNoField, 0, kMember);
+        return st != nullptr;
+    }
+
+    DpTable(const lqrx_dp_desc *d, DpKind k, const DpPtrs &p) : kind(k)
+    {
+        const int64_t n = d->n, m = d->m, N = d->N;
+        const int64_t kAB = d->knot_stride_AB ? N - 1 : 1, kQR = d->knot_stride_QR ? N - 1 : 1;
+        const int64_t kP = d->p_mode ? N : 1;
+        add("A", p.A, DPF(A), n * n * kAB);
+        add("B", p.B, DPF(B), n * m * kAB);
+        if (k >= DP_AFFINE) add("c", p.c, DPF(c), n * kAB);
+        add("Q", p.Q, DPF(Q), n * n * kQR);
+        add("R", p.R, DPF(R), m * m * kQR);
+        if (k >= DP_CROSS) add("M", p.M, DPF(M), m * n * kQR);
+        add("Qf", p.Qf, DPF(Qf), n * n);
+        add("x0", p.x0, DPF(x0), n);
+        if (k >= DP_LINEAR && open("lin", p.lin)) {
+            add("lin->q", p.lin->q, DPF(q), n * kQR, kMember);
+            add("lin->r", p.lin->r, DPF(r), m * kQR, kMember);
+            add("lin->qf", p.lin->qf, DPF(qf), n, kMember);
+            add("lin->d", p.lin->d, DPF(d), m * (N - 1), kMember | kOut);
+            add("lin->p", p.lin->p, DPF(p), n * kP, kMember | kOut);
+        }
+        if (k >= DP_VALUE && open("val", p.val)) {
+            add("val->s", p.val->s, DPF(vs), kP, kMember | kOut);
+            add("val->dV", p.val->dV, DPF(vdV), 1, kMember | kOut | kOptional);
+            iJ = nrows;
+            add("val->J", p.val->J, kNoField, 1, kMember | kOut | kOptional);
+        }
+        add("K", p.K, DPF(K), m * n * (N - 1), kOut);
+        add("P", p.P, DPF(P), n * n * kP, kOut);
+        add("X", p.X, DPF(X), n * N, kOut);
+        add("U", p.U, DPF(U), m * (N - 1), kOut);
+    }
+
+    // every required pointer, in argument order — before anything touches the device
+    int check() const
+    {
+        for (int i = 0; i < nrows; ++i)
+            if (!row[i].ptr && !row[i].optional)
+                return set_err(-row[i].arg, "pointer %d (%s) is NULL", row[i].arg, row[i].name);
+        return 0;
+    }
+    void *J() const { return iJ >= 0 ? row[iJ].ptr : nullptr; }
+};
+#undef DPF
+
+// the kernels' arguments of a checked table; lin, aff, cross and value follow from the kind
+lqrx::DpArgs dp_args(const lqrx_dp_desc *d, const DpTable &t, int32_t *info)
+{
+    lqrx::DpArgs a{};
+    for (int i = 0; i < t.nrows; ++i)
+        if (t.row[i].field != kNoField)
+            *reinterpret_cast<void **>(reinterpret_cast<char *>(&a) + t.row[i].field) = t.row[i].ptr;
+    a.lin = t.kind >= DP_LINEAR; a.aff = t.kind >= DP_AFFINE; a.cross = t.kind >= DP_CROSS;
+    a.value = t.kind >= DP_VALUE;
+    a.info = info;
+    a.n = d->n; a.m = d->m; a.N = d->N; a.dtype = d->dtype; a.p_all = d->p_mode;
+    a.batch = d->batch;
+    a.tv_AB = (int)d->knot_stride_AB; a.tv_QR = (int)d->knot_stride_QR;
+    a.layout = d->layout;
+    return a;
+}
+
 // Layout 1 on the MFMA kernel (one trajectory per wave, contiguous blocks wanted): the SoA
-// inputs are transposed to layout 0 in one stream-ordered scratch block, solved, and the
+// buffers are transposed to layout 0 in one stream-ordered scratch block, solved, and the
 // outputs transposed back into the caller's SoA buffers.  Extra HBM traffic: one read + one
 // write of every input and output (2× the algorithmic bytes); the n ≤ 4 kernels read SoA
 // natively instead.
-// A value solve (a.value) stages s as a seventh output when it holds every s_k (p_all); the batch
-// vectors s_1, dV and J are the same in both layouts and are written in place.  J is formed on the
+// A buffer of one element per trajectory (s_1, dV and J of a value solve) is the same in both
+// layouts and is used in place; s is staged like p when it holds every s_k.  J is formed on the
 // layout-0 scratch, before the transposition back.
-hipError_t dp_launch_soa_staged(const lqrx::DpArgs &a, hipStream_t s, void *J = nullptr)
+hipError_t dp_launch_soa_staged(const lqrx_dp_desc *d, const DpTable &t, int32_t *info, hipStream_t s)
 {
-    const int64_t B = a.batch, n = a.n, m = a.m, N = a.N, es = dsize(a.dtype);
-    const int64_t kAB = a.tv_AB ? N - 1 : 1, kQR = a.tv_QR ? N - 1 : 1;
-    // inputs A B Q R Qf x0 [q r qf [c [M]]], outputs K P X U [d p]
-    const int nin = a.cross ? 11 : (a.aff ? 10 : (a.lin ? 9 : 6));
-    const int nout = (a.value && a.p_all) ? 7 : (a.lin ? 6 : 4);
-    const int64_t S_in[11] = {n * n * kAB, n * m * kAB, n * n * kQR, m * m * kQR, n * n, n,
-                              n * kQR, m * kQR, n, n * kAB, m * n * kQR};
-    const int64_t S_out[7] = {m * n * (N - 1), a.p_all ? n * n * N : n * n, n * N, m * (N - 1),
-                              m * (N - 1), a.p_all ? n * N : n, N};
-    const void *in[11] = {a.A, a.B, a.Q, a.R, a.Qf, a.x0, a.q, a.r, a.qf, a.c, a.M};
-    void *out[7] = {a.K, a.P, a.X, a.U, a.d, a.p, a.vs};
-    size_t off[18], total = 0;
-    for (int i = 0; i < nin + nout; ++i) {
+    const int64_t B = d->batch;
+    const int es = (int)dsize(d->dtype);
+    size_t off[DpTable::kMaxRows], total = 0;
+    for (int i = 0; i < t.nrows; ++i) {
         off[i] = total;
-        total += ((size_t)(i < nin ? S_in[i] : S_out[i - nin]) * B * es + 255) & ~(size_t)255;
+        if (t.row[i].elems > 1) total += ((size_t)t.row[i].elems * B * es + 255) & ~(size_t)255;
     }
     void *blk = nullptr;
     hipError_t e = lqrx::scratch_alloc(&blk, total, s);
     if (e != hipSuccess) return e;
-    char *base = (char *)blk;
-    lqrx::DpArgs a0 = a;
-    a0.layout = 0;
-    const void **pin[11] = {&a0.A, &a0.B, &a0.Q, &a0.R, &a0.Qf, &a0.x0, &a0.q, &a0.r, &a0.qf, &a0.c, &a0.M};
-    void **pout[7] = {&a0.K, &a0.P, &a0.X, &a0.U, &a0.d, &a0.p, &a0.vs};
-    for (int i = 0; i < nin && e == hipSuccess; ++i) {        // [S][B] → [B][S]
-        *pin[i] = base + off[i];
-        e = lqrx::batch_transpose(in[i], base + off[i], S_in[i], B, (int)es, s);
+    DpTable t0 = t;
+    for (int i = 0; i < t.nrows; ++i) {
+        const DpRow &r = t.row[i];
+        if (r.elems <= 1) continue;
+        t0.row[i].ptr = (char *)blk + off[i];
+        if (!r.out && e == hipSuccess)                            // [S][B] → [B][S]
+            e = lqrx::batch_transpose(r.ptr, t0.row[i].ptr, r.elems, B, es, s);
     }
-    for (int i = 0; i < nout; ++i) *pout[i] = base + off[nin + i];
+    lqrx_dp_desc d0 = *d;
+    d0.layout = 0;
+    const lqrx::DpArgs a0 = dp_args(&d0, t0, info);
     if (e == hipSuccess) e = lqrx::dp_launch(a0, s);
-    if (e == hipSuccess && J) e = lqrx::dp_value_cost_launch(a0, J, s);
-    for (int i = 0; i < nout && e == hipSuccess; ++i)         // [B][S] → [S][B]
-        e = lqrx::batch_transpose(base + off[nin + i], out[i], B, S_out[i], (int)es, s);
+    if (e == hipSuccess && t.J()) e = lqrx::dp_value_cost_launch(a0, t.J(), s);
+    for (int i = 0; i < t.nrows && e == hipSuccess; ++i)          // [B][S] → [S][B]
+        if (t.row[i].out && t.row[i].elems > 1)
+            e = lqrx::batch_transpose(t0.row[i].ptr, t.row[i].ptr, B, t.row[i].elems, es, s);
     hipError_t ef = lqrx::scratch_free(blk, s);
     return e != hipSuccess ? e : ef;
 }
+
+// ---- host staging: the device twins of a call's host buffers (the *_host entries) ----
+enum HostDir { H_IN, H_OUT, H_SCRATCH };   // copied in; copied back; device only (an info nobody reads)
+struct HostBuf {
+    void *host;      // NULL (an optional buffer the caller left out): no twin, unless H_SCRATCH
+    size_t bytes;
+    HostDir dir;
+};
+HostBuf host_in(const void *p, size_t bytes) { return HostBuf{const_cast<void *>(p), bytes, H_IN}; }
+HostBuf host_info(int32_t *info, size_t batch) { return HostBuf{info, 4 * batch, info ? H_OUT : H_SCRATCH}; }
+
+struct HostStage {
+    DevBuf dev[DpTable::kMaxRows + 1];
+    void *operator[](int i) const { return dev[i].p; }
+    int upload(const HostBuf *l, int n)
+    {
+        for (int i = 0; i < n; ++i) {
+            if (!l[i].host && l[i].dir != H_SCRATCH) continue;
+            if (int st = dev_alloc(dev[i], l[i].bytes, "hipMalloc (host staging)")) return st;
+            if (l[i].dir != H_IN) continue;
+            const hipError_t e = hipMemcpy(dev[i].p, l[i].host, l[i].bytes, hipMemcpyHostToDevice);
+            if (e != hipSuccess) return hip_err(e, "H2D");
+        }
+        return 0;
+    }
+    int download(const HostBuf *l, int n) const
+    {
+        for (int i = 0; i < n; ++i) {
+            if (l[i].dir != H_OUT || !dev[i].p) continue;
+            const hipError_t e = hipMemcpy(l[i].host, dev[i].p, l[i].bytes, hipMemcpyDeviceToHost);
+            if (e != hipSuccess) return hip_err(e, "D2H");
+        }
+        return 0;
+    }
+};
 } // namespace
 
 extern "C" {
@@ -232,139 +368,18 @@ int lqrx_device_available(void)
 }   // extern "C"
 
 namespace {
-// Pointer checks of lqrx_dp_solve_affine[_host], in argument order (desc 1, A 2, B 3, c 4,
-// Q 5 … x0 8, lin 9, K 10 … U 13) — before anything touches the device
-int check_affine_ptrs(const void *A, const void *B, const void *c, const void *Q, const void *R,
-                      const void *Qf, const void *x0, const lqrx_dp_linear *lin, void *K, void *P,
-                      void *X, void *U)
+// launch of a checked table on device pointers; 1 where a trajectory's info is non-zero (null
+// stream only: the call is then synchronous)
+int dp_run(const lqrx_dp_desc *d, const DpTable &t, int32_t *info, void *stream)
 {
-    const void *in[7] = {A, B, c, Q, R, Qf, x0};
-    static const char *inm[7] = {"A", "B", "c", "Q", "R", "Qf", "x0"};
-    for (int i = 0; i < 7; ++i)
-        if (!in[i]) return set_err(-(i + 2), "input pointer %d (%s) is NULL", i + 2, inm[i]);
-    if (!lin) return set_err(-9, "lin is NULL (pass zero q, r, qf for a problem without linear cost terms)");
-    const void *lp[5] = {lin->q, lin->r, lin->qf, lin->d, lin->p};
-    static const char *nm[5] = {"q", "r", "qf", "d", "p"};
-    for (int i = 0; i < 5; ++i)
-        if (!lp[i]) return set_err(-9, "lin->%s is NULL", nm[i]);
-    const void *out[4] = {K, P, X, U};
-    for (int i = 0; i < 4; ++i)
-        if (!out[i]) return set_err(-(i + 10), "output pointer %d is NULL", i + 10);
-    return 0;
-}
-
-// Pointer checks of lqrx_dp_solve_cross[_host], in argument order (desc 1, A 2, B 3, c 4, Q 5,
-// R 6, M 7, Qf 8, x0 9, lin 10, K 11 … U 14) — before anything touches the device
-int check_cross_ptrs(const void *A, const void *B, const void *c, const void *Q, const void *R,
-                     const void *M, const void *Qf, const void *x0, const lqrx_dp_linear *lin, void *K,
-                     void *P, void *X, void *U)
-{
-    const void *in[8] = {A, B, c, Q, R, M, Qf, x0};
-    static const char *inm[8] = {"A", "B", "c", "Q", "R", "M", "Qf", "x0"};
-    for (int i = 0; i < 8; ++i)
-        if (!in[i]) return set_err(-(i + 2), "input pointer %d (%s) is NULL", i + 2, inm[i]);
-    if (!lin) return set_err(-10, "lin is NULL (pass zero q, r, qf for a problem without linear cost terms)");
-    const void *lp[5] = {lin->q, lin->r, lin->qf, lin->d, lin->p};
-    static const char *nm[5] = {"q", "r", "qf", "d", "p"};
-    for (int i = 0; i < 5; ++i)
-        if (!lp[i]) return set_err(-10, "lin->%s is NULL", nm[i]);
-    const void *out[4] = {K, P, X, U};
-    for (int i = 0; i < 4; ++i)
-        if (!out[i]) return set_err(-(i + 11), "output pointer %d is NULL", i + 11);
-    return 0;
-}
-
-// Pointer checks of lqrx_dp_solve_value[_host], in argument order (desc 1, A 2, B 3, c 4, Q 5,
-// R 6, M 7, Qf 8, x0 9, lin 10, val 11, K 12 … U 15) — before anything touches the device
-int check_value_ptrs(const void *A, const void *B, const void *c, const void *Q, const void *R,
-                     const void *M, const void *Qf, const void *x0, const lqrx_dp_linear *lin,
-                     const lqrx_dp_value *val, void *K, void *P, void *X, void *U)
-{
-    const void *in[8] = {A, B, c, Q, R, M, Qf, x0};
-    static const char *inm[8] = {"A", "B", "c", "Q", "R", "M", "Qf", "x0"};
-    for (int i = 0; i < 8; ++i)
-        if (!in[i]) return set_err(-(i + 2), "input pointer %d (%s) is NULL", i + 2, inm[i]);
-    if (!lin) return set_err(-10, "lin is NULL (pass zero q, r, qf for a problem without linear cost terms)");
-    const void *lp[5] = {lin->q, lin->r, lin->qf, lin->d, lin->p};
-    static const char *nm[5] = {"q", "r", "qf", "d", "p"};
-    for (int i = 0; i < 5; ++i)
-        if (!lp[i]) return set_err(-10, "lin->%s is NULL", nm[i]);
-    if (!val) return set_err(-11, "val is NULL (its member s is required; dV and J may be NULL)");
-    if (!val->s) return set_err(-11, "val->s is NULL");
-    const void *out[4] = {K, P, X, U};
-    for (int i = 0; i < 4; ++i)
-        if (!out[i]) return set_err(-(i + 12), "output pointer %d is NULL", i + 12);
-    return 0;
-}
-
-// lqrx_dp_solve, lqrx_dp_solve_linear (lin != NULL), lqrx_dp_solve_affine (aff: c and lin,
-// checked by check_affine_ptrs before this) and lqrx_dp_solve_cross (cross, with aff: c, M and
-// lin, checked by check_cross_ptrs) and lqrx_dp_solve_value (value, with cross: val on top,
-// checked by check_value_ptrs); argument numbers in error codes follow the calling entry
-// point's signature
-int dp_solve_impl(const lqrx_dp_desc *d, const void *A, const void *B, const void *Q,
-                  const void *R, const void *Qf, const void *x0, const lqrx_dp_linear *lin,
-                  void *K, void *P, void *X, void *U, int32_t *info, void *stream,
-                  const void *c = nullptr, bool aff = false, const void *M = nullptr,
-                  bool cross = false, const lqrx_dp_value *val = nullptr, bool value = false)
-{
-    int st = validate_dp(d);
-    if (st) return st;
-    if (d->batch == 0) return 0;
-    if (value) {
-        if ((st = check_value_ptrs(A, B, c, Q, R, M, Qf, x0, lin, val, K, P, X, U))) return st;
-    } else if (cross) {
-        if ((st = check_cross_ptrs(A, B, c, Q, R, M, Qf, x0, lin, K, P, X, U))) return st;
-    } else if (aff) {
-        if ((st = check_affine_ptrs(A, B, c, Q, R, Qf, x0, lin, K, P, X, U))) return st;
-    } else {
-        const int o = lin ? 1 : 0;   // lqrx_dp_solve_linear: lin is argument 8, outputs shift by one
-        const void *in[6] = {A, B, Q, R, Qf, x0};
-        for (int i = 0; i < 6; ++i)
-            if (!in[i]) return set_err(-(i + 2), "input pointer %d is NULL", i + 2);
-        if (lin) {
-            const void *lp[5] = {lin->q, lin->r, lin->qf, lin->d, lin->p};
-            static const char *nm[5] = {"q", "r", "qf", "d", "p"};
-            for (int i = 0; i < 5; ++i)
-                if (!lp[i]) return set_err(-8, "lin->%s is NULL", nm[i]);
-        }
-        void *out[4] = {K, P, X, U};
-        for (int i = 0; i < 4; ++i)
-            if (!out[i]) return set_err(-(i + 8 + o), "output pointer %d is NULL", i + 8 + o);
-    }
-
-    lqrx::DpArgs a{};
-    if (lin) {
-        a.lin = 1;
-        a.q = lin->q; a.r = lin->r; a.qf = lin->qf; a.d = lin->d; a.p = lin->p;
-    }
-    if (aff) {
-        a.aff = 1;
-        a.c = c;
-    }
-    if (cross) {
-        a.cross = 1;
-        a.M = M;
-    }
-    if (value) {
-        a.value = 1;
-        a.vs = val->s;
-        a.vdV = val->dV;
-    }
-    a.A = A; a.B = B; a.Q = Q; a.R = R; a.Qf = Qf; a.x0 = x0;
-    a.K = K; a.P = P; a.X = X; a.U = U; a.info = info;
-    a.n = d->n; a.m = d->m; a.N = d->N; a.dtype = d->dtype; a.p_all = d->p_mode;
-    a.batch = d->batch;
-    a.tv_AB = (int)d->knot_stride_AB; a.tv_QR = (int)d->knot_stride_QR;
-    a.layout = d->layout;
     hipStream_t s = (hipStream_t)stream;
     hipError_t e;
-    void *J = value ? val->J : nullptr;           // V_1(x0): one small kernel behind the solve
     if (d->layout == 1 && !lqrx::dp_lane_supported(d->n, d->m)) {
-        e = dp_launch_soa_staged(a, s, J);        // MFMA kernel: convert, solve, convert back
+        e = dp_launch_soa_staged(d, t, info, s);  // MFMA kernel: convert, solve, convert back
     } else {
+        const lqrx::DpArgs a = dp_args(d, t, info);
         e = lqrx::dp_launch(a, s);
-        if (e == hipSuccess && J) e = lqrx::dp_value_cost_launch(a, J, s);
+        if (e == hipSuccess && t.J()) e = lqrx::dp_value_cost_launch(a, t.J(), s);   // V_1(x0): one small kernel behind the solve
     }
     if (e == hipErrorNotSupported)
         return set_err(LQRX_ERR_UNSUPPORTED, "no kernel for n=%d m=%d", d->n, d->m);
@@ -383,76 +398,40 @@ int dp_solve_impl(const lqrx_dp_desc *d, const void *A, const void *B, const voi
     return 0;
 }
 
-int dp_solve_host_impl(const lqrx_dp_desc *d, const void *A, const void *B, const void *Q,
-                       const void *R, const void *Qf, const void *x0, const lqrx_dp_linear *lin,
-                       void *K, void *P, void *X, void *U, int32_t *info,
-                       const void *c = nullptr, bool aff = false, const void *M = nullptr,
-                       bool cross = false, const lqrx_dp_value *val = nullptr, bool value = false)
+// Every DP solve entry on device pointers.  Order of the checks: descriptor, batch == 0 (a no-op),
+// pointers in the argument order of the entry that was called.
+int dp_solve_impl(const lqrx_dp_desc *d, DpKind kind, const DpPtrs &p, void *stream)
 {
     int st = validate_dp(d);
     if (st) return st;
     if (d->batch == 0) return 0;
-    if (value) {
-        if ((st = check_value_ptrs(A, B, c, Q, R, M, Qf, x0, lin, val, K, P, X, U))) return st;
-    } else if (cross) {
-        if ((st = check_cross_ptrs(A, B, c, Q, R, M, Qf, x0, lin, K, P, X, U))) return st;
-    } else if (aff && (st = check_affine_ptrs(A, B, c, Q, R, Qf, x0, lin, K, P, X, U))) return st;
-    const int o = lin ? 1 : 0;
-    const size_t s = dsize(d->dtype), bt = (size_t)d->batch;
-    const size_t n = d->n, m = d->m, N = d->N;
-    const size_t kAB = d->knot_stride_AB ? N - 1 : 1, kQR = d->knot_stride_QR ? N - 1 : 1;
-    const int nin = cross ? 11 : (aff ? 10 : (lin ? 9 : 6)), nout = lin ? 6 : 4;
-    const size_t szin[11] = {n * n * kAB, n * m * kAB, n * n * kQR, m * m * kQR, n * n, n,
-                             n * kQR, m * kQR, n, n * kAB, m * n * kQR};
-    const void *hin[11] = {A, B, Q, R, Qf, x0, lin ? lin->q : nullptr, lin ? lin->r : nullptr,
-                           lin ? lin->qf : nullptr, c, M};
-    const size_t szout[6] = {m * n * (N - 1), d->p_mode ? n * n * N : n * n, n * N, m * (N - 1),
-                             m * (N - 1), d->p_mode ? n * N : n};
-    void *hout[6] = {K, P, X, U, lin ? lin->d : nullptr, lin ? lin->p : nullptr};
-    DevBuf din[11], dout[6], dinfo;
-    for (int i = 0; i < nin; ++i) {
-        if (!hin[i]) return set_err(i < 6 ? -(i + 2) : -8, "input pointer %s is NULL",
-                                    i < 6 ? "" : "in lin");
-        if ((st = dev_alloc(din[i], szin[i] * s * bt, "hipMalloc input"))) return st;
-        hipError_t e = hipMemcpy(din[i].p, hin[i], szin[i] * s * bt, hipMemcpyHostToDevice);
-        if (e != hipSuccess) return hip_err(e, "H2D");
-    }
-    for (int i = 0; i < nout; ++i) {
-        if (!hout[i]) return set_err(i < 4 ? -(i + 8 + o) : -8, "output pointer %s is NULL",
-                                     i < 4 ? "" : "in lin");
-        if ((st = dev_alloc(dout[i], szout[i] * s * bt, "hipMalloc output"))) return st;
-    }
-    if ((st = dev_alloc(dinfo, 4 * bt, "hipMalloc info"))) return st;
-    // value outputs: s (every s_k with p_mode 1), and dV, J where asked for
-    const size_t szval[3] = {d->p_mode ? N : 1, 1, 1};
-    void *hval[3] = {value ? val->s : nullptr, value ? val->dV : nullptr, value ? val->J : nullptr};
-    DevBuf dval[3];
-    for (int i = 0; i < 3; ++i)
-        if (hval[i] && (st = dev_alloc(dval[i], szval[i] * s * bt, "hipMalloc value output"))) return st;
-    const lqrx_dp_value dv{dval[0].p, dval[1].p, dval[2].p};
-    lqrx_dp_linear dl{};
-    if (lin) {
-        dl.q = din[6].p; dl.r = din[7].p; dl.qf = din[8].p; dl.d = dout[4].p; dl.p = dout[5].p;
-    }
-    st = dp_solve_impl(d, din[0].p, din[1].p, din[2].p, din[3].p, din[4].p, din[5].p,
-                       lin ? &dl : nullptr, dout[0].p, dout[1].p, dout[2].p, dout[3].p,
-                       (int32_t *)dinfo.p, nullptr, aff ? din[9].p : nullptr, aff,
-                       cross ? din[10].p : nullptr, cross, value ? &dv : nullptr, value);
+    const DpTable t(d, kind, p);
+    if ((st = t.check())) return st;
+    return dp_run(d, t, p.info, stream);
+}
+
+// Every DP solve entry on host pointers: the same checks, before any device call; then one device
+// twin per buffer of the table, the solve on the null stream, and the outputs copied back.
+int dp_solve_host_impl(const lqrx_dp_desc *d, DpKind kind, const DpPtrs &p)
+{
+    int st = validate_dp(d);
+    if (st) return st;
+    if (d->batch == 0) return 0;
+    const DpTable t(d, kind, p);
+    if ((st = t.check())) return st;
+    const size_t bt = (size_t)d->batch, es = dsize(d->dtype);
+    HostBuf hb[DpTable::kMaxRows + 1];
+    for (int i = 0; i < t.nrows; ++i)
+        hb[i] = HostBuf{t.row[i].ptr, (size_t)t.row[i].elems * es * bt, t.row[i].out ? H_OUT : H_IN};
+    hb[t.nrows] = host_info(p.info, bt);
+    HostStage dev;
+    if ((st = dev.upload(hb, t.nrows + 1))) return st;
+    DpTable td = t;
+    for (int i = 0; i < t.nrows; ++i) td.row[i].ptr = dev[i];
+    st = dp_run(d, td, (int32_t *)dev[t.nrows], nullptr);
     if (st < 0) return st;
-    for (int i = 0; i < nout; ++i) {
-        hipError_t e = hipMemcpy(hout[i], dout[i].p, szout[i] * s * bt, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return hip_err(e, "D2H");
-    }
-    for (int i = 0; i < 3; ++i) {
-        if (!hval[i]) continue;
-        hipError_t e = hipMemcpy(hval[i], dval[i].p, szval[i] * s * bt, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return hip_err(e, "D2H value");
-    }
-    if (info) {
-        hipError_t e = hipMemcpy(info, dinfo.p, 4 * bt, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return hip_err(e, "D2H info");
-    }
-    return st;
+    const int e = dev.download(hb, t.nrows + 1);
+    return e ? e : st;
 }
 } // namespace
 
@@ -462,14 +441,14 @@ int lqrx_dp_solve(const lqrx_dp_desc *d, const void *A, const void *B, const voi
                   const void *R, const void *Qf, const void *x0, void *K, void *P, void *X,
                   void *U, int32_t *info, void *stream)
 {
-    return dp_solve_impl(d, A, B, Q, R, Qf, x0, nullptr, K, P, X, U, info, stream);
+    return dp_solve_impl(d, DP_PLAIN, DpPtrs{A, B, nullptr, Q, R, nullptr, Qf, x0, nullptr, nullptr, K, P, X, U, info}, stream);
 }
 
 int lqrx_dp_solve_host(const lqrx_dp_desc *d, const void *A, const void *B, const void *Q,
                        const void *R, const void *Qf, const void *x0, void *K, void *P,
                        void *X, void *U, int32_t *info)
 {
-    return dp_solve_host_impl(d, A, B, Q, R, Qf, x0, nullptr, K, P, X, U, info);
+    return dp_solve_host_impl(d, DP_PLAIN, DpPtrs{A, B, nullptr, Q, R, nullptr, Qf, x0, nullptr, nullptr, K, P, X, U, info});
 }
 
 // compute_ctg!(K, solver, prob) / compute_gain!(K, solver, prob) for a batch
@@ -507,8 +486,8 @@ int lqrx_dp_compute_ctg(const lqrx_dp_desc *d, const void *A, const void *B, con
         (void)lqrx::scratch_free(blk, s);
         return hip_err(e, "compute_ctg x0");
     }
-    st = dp_solve_impl(&d2, A, B, Q, R, P, b + ox, nullptr, K, P_ ? P_ : (void *)(b + oP), b + oX, b + oU,
-                       info, stream);
+    st = dp_solve_impl(&d2, DP_PLAIN, DpPtrs{A, B, nullptr, Q, R, nullptr, P, b + ox, nullptr, nullptr, K,
+                                             P_ ? P_ : (void *)(b + oP), b + oX, b + oU, info}, stream);
     e = lqrx::scratch_free(blk, s);
     if (st) return st;
     return e == hipSuccess ? 0 : hip_err(e, "compute_ctg scratch free");
@@ -526,27 +505,19 @@ int lqrx_dp_compute_ctg_host(const lqrx_dp_desc *d, const void *A, const void *B
     if (st) return st;
     if (d2.batch == 0) return 0;
     const void *hin[5] = {A, B, Q, R, P};
-    const size_t es = dsize(d2.dtype), bt = (size_t)d2.batch, n = d2.n, m = d2.m;
-    const size_t szin[5] = {n * n, n * m, n * n, m * m, n * n};
-    DevBuf din[5], dK, dP, dinfo;
-    for (int i = 0; i < 5; ++i) {
+    for (int i = 0; i < 5; ++i)
         if (!hin[i]) return set_err(-(i + 2), "input pointer %d is NULL", i + 2);
-        if ((st = dev_alloc(din[i], szin[i] * es * bt, "hipMalloc input"))) return st;
-        const hipError_t e = hipMemcpy(din[i].p, hin[i], szin[i] * es * bt, hipMemcpyHostToDevice);
-        if (e != hipSuccess) return hip_err(e, "H2D");
-    }
     if (!K) return set_err(-7, "K is NULL");
-    if ((st = dev_alloc(dK, m * n * es * bt, "hipMalloc K"))) return st;
-    if (P_ && (st = dev_alloc(dP, n * n * es * bt, "hipMalloc P_"))) return st;
-    if ((st = dev_alloc(dinfo, 4 * bt, "hipMalloc info"))) return st;
-    st = lqrx_dp_compute_ctg(&d2, din[0].p, din[1].p, din[2].p, din[3].p, din[4].p, dK.p, P_ ? dP.p : nullptr,
-                             (int32_t *)dinfo.p, nullptr);
+    const size_t bt = (size_t)d2.batch, n = d2.n, m = d2.m, eb = dsize(d2.dtype) * bt;   // bytes per element row
+    const size_t nn = n * n * eb, nm = n * m * eb, mm = m * m * eb;
+    const HostBuf hb[8] = {host_in(A, nn), host_in(B, nm), host_in(Q, nn), host_in(R, mm), host_in(P, nn),
+                           HostBuf{K, nm, H_OUT}, HostBuf{P_, nn, H_OUT}, host_info(info, bt)};
+    HostStage dev;
+    if ((st = dev.upload(hb, 8))) return st;
+    st = lqrx_dp_compute_ctg(&d2, dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], dev[6], (int32_t *)dev[7], nullptr);
     if (st < 0) return st;
-    hipError_t e = hipMemcpy(K, dK.p, m * n * es * bt, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && P_) e = hipMemcpy(P_, dP.p, n * n * es * bt, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && info) e = hipMemcpy(info, dinfo.p, 4 * bt, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return hip_err(e, "D2H");
-    return st;
+    const int e = dev.download(hb, 8);
+    return e ? e : st;
 }
 
 int lqrx_dp_solve_linear(const lqrx_dp_desc *d, const void *A, const void *B, const void *Q,
@@ -554,8 +525,7 @@ int lqrx_dp_solve_linear(const lqrx_dp_desc *d, const void *A, const void *B, co
                          const lqrx_dp_linear *lin, void *K, void *P, void *X, void *U,
                          int32_t *info, void *stream)
 {
-    if (!lin) return set_err(-8, "lin is NULL");
-    return dp_solve_impl(d, A, B, Q, R, Qf, x0, lin, K, P, X, U, info, stream);
+    return dp_solve_impl(d, DP_LINEAR, DpPtrs{A, B, nullptr, Q, R, nullptr, Qf, x0, lin, nullptr, K, P, X, U, info}, stream);
 }
 
 int lqrx_dp_solve_linear_host(const lqrx_dp_desc *d, const void *A, const void *B,
@@ -563,8 +533,7 @@ int lqrx_dp_solve_linear_host(const lqrx_dp_desc *d, const void *A, const void *
                               const lqrx_dp_linear *lin, void *K, void *P, void *X, void *U,
                               int32_t *info)
 {
-    if (!lin) return set_err(-8, "lin is NULL");
-    return dp_solve_host_impl(d, A, B, Q, R, Qf, x0, lin, K, P, X, U, info);
+    return dp_solve_host_impl(d, DP_LINEAR, DpPtrs{A, B, nullptr, Q, R, nullptr, Qf, x0, lin, nullptr, K, P, X, U, info});
 }
 
 // affine dynamics x⁺ = A x + B u + c: the linear-terms solve with p̃ = p + P c_k (see lqrx.h)
@@ -573,7 +542,7 @@ int lqrx_dp_solve_affine(const lqrx_dp_desc *d, const void *A, const void *B, co
                          const lqrx_dp_linear *lin, void *K, void *P, void *X, void *U,
                          int32_t *info, void *stream)
 {
-    return dp_solve_impl(d, A, B, Q, R, Qf, x0, lin, K, P, X, U, info, stream, c, true);
+    return dp_solve_impl(d, DP_AFFINE, DpPtrs{A, B, c, Q, R, nullptr, Qf, x0, lin, nullptr, K, P, X, U, info}, stream);
 }
 
 int lqrx_dp_solve_affine_host(const lqrx_dp_desc *d, const void *A, const void *B, const void *c,
@@ -581,7 +550,7 @@ int lqrx_dp_solve_affine_host(const lqrx_dp_desc *d, const void *A, const void *
                               const lqrx_dp_linear *lin, void *K, void *P, void *X, void *U,
                               int32_t *info)
 {
-    return dp_solve_host_impl(d, A, B, Q, R, Qf, x0, lin, K, P, X, U, info, c, true);
+    return dp_solve_host_impl(d, DP_AFFINE, DpPtrs{A, B, c, Q, R, nullptr, Qf, x0, lin, nullptr, K, P, X, U, info});
 }
 
 // cost cross term uᵀMx on top of the affine solve: G = BᵀPA + M_k (see lqrx.h)
@@ -590,7 +559,7 @@ int lqrx_dp_solve_cross(const lqrx_dp_desc *d, const void *A, const void *B, con
                         const lqrx_dp_linear *lin, void *K, void *P, void *X, void *U,
                         int32_t *info, void *stream)
 {
-    return dp_solve_impl(d, A, B, Q, R, Qf, x0, lin, K, P, X, U, info, stream, c, true, M, true);
+    return dp_solve_impl(d, DP_CROSS, DpPtrs{A, B, c, Q, R, M, Qf, x0, lin, nullptr, K, P, X, U, info}, stream);
 }
 
 int lqrx_dp_solve_cross_host(const lqrx_dp_desc *d, const void *A, const void *B, const void *c,
@@ -598,7 +567,7 @@ int lqrx_dp_solve_cross_host(const lqrx_dp_desc *d, const void *A, const void *B
                              const void *x0, const lqrx_dp_linear *lin, void *K, void *P, void *X,
                              void *U, int32_t *info)
 {
-    return dp_solve_host_impl(d, A, B, Q, R, Qf, x0, lin, K, P, X, U, info, c, true, M, true);
+    return dp_solve_host_impl(d, DP_CROSS, DpPtrs{A, B, c, Q, R, M, Qf, x0, lin, nullptr, K, P, X, U, info});
 }
 
 // the value function's constant on top of the cross solve: s, dV = Σ hᵀd, J = V_1(x0) (see lqrx.h)
@@ -607,8 +576,7 @@ int lqrx_dp_solve_value(const lqrx_dp_desc *d, const void *A, const void *B, con
                         const lqrx_dp_linear *lin, const lqrx_dp_value *val, void *K, void *P,
                         void *X, void *U, int32_t *info, void *stream)
 {
-    return dp_solve_impl(d, A, B, Q, R, Qf, x0, lin, K, P, X, U, info, stream, c, true, M, true,
-                         val, true);
+    return dp_solve_impl(d, DP_VALUE, DpPtrs{A, B, c, Q, R, M, Qf, x0, lin, val, K, P, X, U, info}, stream);
 }
 
 int lqrx_dp_solve_value_host(const lqrx_dp_desc *d, const void *A, const void *B, const void *c,
@@ -616,8 +584,7 @@ int lqrx_dp_solve_value_host(const lqrx_dp_desc *d, const void *A, const void *B
                              const void *x0, const lqrx_dp_linear *lin, const lqrx_dp_value *val,
                              void *K, void *P, void *X, void *U, int32_t *info)
 {
-    return dp_solve_host_impl(d, A, B, Q, R, Qf, x0, lin, K, P, X, U, info, c, true, M, true, val,
-                              true);
+    return dp_solve_host_impl(d, DP_VALUE, DpPtrs{A, B, c, Q, R, M, Qf, x0, lin, val, K, P, X, U, info});
 }
 
 } // extern "C"
@@ -699,20 +666,16 @@ int lqrx_dp_costates_host(const lqrx_dp_desc *d, const void *A, const void *B, c
     const void *hin[12] = {A, B, Q, R, M, Qf, q, r, qf, K, X, U};
     const size_t szin[12] = {n * n * kAB, n * m * kAB, n * n * kQR, m * m * kQR, m * n * kQR, n * n,
                              n * kQR, m * kQR, n, m * n * (N - 1), n * N, m * (N - 1)};
-    DevBuf din[12], dlam;
-    for (int i = 0; i < 12; ++i) {
-        if (!hin[i]) continue;   // M, q, r, qf: NULL means zero
-        if ((st = dev_alloc(din[i], szin[i] * es * bt, "hipMalloc input"))) return st;
-        const hipError_t e = hipMemcpy(din[i].p, hin[i], szin[i] * es * bt, hipMemcpyHostToDevice);
-        if (e != hipSuccess) return hip_err(e, "H2D");
-    }
-    if ((st = dev_alloc(dlam, n * N * es * bt, "hipMalloc lam"))) return st;
-    st = lqrx_dp_costates(d, din[0].p, din[1].p, din[2].p, din[3].p, din[4].p, din[5].p, din[6].p, din[7].p,
-                          din[8].p, din[9].p, din[10].p, din[11].p, dlam.p, nullptr);
+    HostBuf hb[13];
+    for (int i = 0; i < 12; ++i) hb[i] = host_in(hin[i], szin[i] * es * bt);   // M, q, r, qf: NULL means zero
+    hb[12] = HostBuf{lam, n * N * es * bt, H_OUT};
+    HostStage dev;
+    if ((st = dev.upload(hb, 13))) return st;
+    st = lqrx_dp_costates(d, dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], dev[6], dev[7], dev[8], dev[9], dev[10],
+                          dev[11], dev[12], nullptr);
     if (st < 0) return st;
-    const hipError_t e = hipMemcpy(lam, dlam.p, n * N * es * bt, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return hip_err(e, "D2H lam");
-    return st;
+    const int e = dev.download(hb, 13);
+    return e ? e : st;
 }
 
 // Gradients of a loss ℓ(X, U) through the solve: one more cross solve with ∂ℓ/∂X, ∂ℓ/∂U as the
@@ -763,14 +726,11 @@ int lqrx_dp_solve_adjoint(const lqrx_dp_desc *d, const void *A, const void *B, c
     }
     if (e == hipSuccess) {
         what = "adjoint solve";
-        lqrx::DpArgs a{};
-        a.lin = a.aff = a.cross = 1;
-        a.A = A; a.B = B; a.Q = Q; a.R = R; a.Qf = Qf; a.x0 = x0a; a.c = ca; a.M = M;
-        a.q = qa; a.r = grad->gU; a.qf = qfa; a.d = da; a.p = pa;
-        a.K = Ka; a.P = Pa; a.X = Xa; a.U = Ua; a.info = infoa;
-        a.n = d->n; a.m = d->m; a.N = d->N; a.dtype = d->dtype; a.p_all = 0; a.batch = d->batch;
-        a.tv_AB = tvAB; a.tv_QR = 1; a.layout = 0;
-        e = lqrx::dp_launch(a, s);
+        lqrx_dp_desc d1 = *d;   // layout 0 and per-knot Q, R already; P_1 and p_1 only
+        d1.p_mode = 0;
+        const lqrx_dp_linear la{qa, grad->gU, qfa, da, pa};
+        const DpTable t(&d1, DP_CROSS, DpPtrs{A, B, ca, Q, R, M, Qf, x0a, &la, nullptr, Ka, Pa, Xa, Ua, infoa});
+        e = lqrx::dp_launch(dp_args(&d1, t, infoa), s);
     }
     if (e == hipSuccess) {
         what = "adjoint costates";
@@ -1326,10 +1286,16 @@ std::vector<Shard> make_shards(int64_t B, const int32_t *devices, int32_t ndev)
     return sh;
 }
 
-int check_devices(const int32_t *devices, int32_t ndev, int ai_dev, int ai_ndev)
+// devices / ndev of a _host_devices entry: the arguments themselves (no device call) …
+int check_devices_args(const int32_t *devices, int32_t ndev, int ai_dev, int ai_ndev)
 {
     if (ndev < 1) return set_err(-ai_ndev, "ndev must be >= 1 (got %d)", ndev);
     if (!devices) return set_err(-ai_dev, "devices is NULL");
+    return 0;
+}
+// … and every ordinal against hipGetDeviceCount
+int check_device_ordinals(const int32_t *devices, int32_t ndev, int ai_dev)
+{
     int cnt = 0;
     const hipError_t e = hipGetDeviceCount(&cnt);
     if (e != hipSuccess) return set_err(LQRX_ERR_NODEVICE, "hipGetDeviceCount: %s", hipGetErrorString(e));
@@ -1337,6 +1303,11 @@ int check_devices(const int32_t *devices, int32_t ndev, int ai_dev, int ai_ndev)
         if (devices[i] < 0 || devices[i] >= cnt)
             return set_err(-ai_dev, "devices[%d] = %d is not a device (0..%d)", i, devices[i], cnt - 1);
     return 0;
+}
+int check_devices(const int32_t *devices, int32_t ndev, int ai_dev, int ai_ndev)
+{
+    const int st = check_devices_args(devices, ndev, ai_dev, ai_ndev);
+    return st ? st : check_device_ordinals(devices, ndev, ai_dev);
 }
 
 // one host array of S elements per trajectory: the shard's slice ↔ a packed device buffer of
@@ -1403,57 +1374,44 @@ template <typename F> int run_shards(std::vector<Shard> &sh, const int32_t *info
     return 0;
 }
 
-int dp_solve_host_devices_impl(const lqrx_dp_desc *d, const void *A, const void *B, const void *Q,
-                               const void *R, const void *Qf, const void *x0, const lqrx_dp_linear *lin,
-                               void *K, void *P, void *X, void *U, int32_t *info, const int32_t *devices,
+// The _host_devices entries (plain and linear): descriptor; devices and ndev, the two arguments
+// behind info; pointers (a non-empty batch); the ordinals, the first device call; batch == 0 is a
+// no-op.  Each shard stages its slice of every buffer of the table on its own device and stream.
+int dp_solve_host_devices_impl(const lqrx_dp_desc *d, DpKind kind, const DpPtrs &p, const int32_t *devices,
                                int32_t ndev)
 {
     int st = validate_dp(d);
     if (st) return st;
-    const int o = lin ? 1 : 0;
-    if ((st = check_devices(devices, ndev, 13 + o, 14 + o))) return st;
+    const DpTable t(d, kind, p);
+    if ((st = check_devices_args(devices, ndev, t.narg + 2, t.narg + 3))) return st;
+    if (d->batch && (st = t.check())) return st;
+    if ((st = check_device_ordinals(devices, ndev, t.narg + 2))) return st;
     if (d->batch == 0) return 0;
-    const size_t es = dsize(d->dtype), n = d->n, m = d->m, N = d->N;
-    const size_t kAB = d->knot_stride_AB ? N - 1 : 1, kQR = d->knot_stride_QR ? N - 1 : 1;
-    const int nin = lin ? 9 : 6, nout = lin ? 6 : 4;
-    const size_t szin[9] = {n * n * kAB, n * m * kAB, n * n * kQR, m * m * kQR, n * n, n, n * kQR, m * kQR, n};
-    const void *hin[9] = {A, B, Q, R, Qf, x0, lin ? lin->q : nullptr, lin ? lin->r : nullptr,
-                          lin ? lin->qf : nullptr};
-    const size_t szout[6] = {m * n * (N - 1), d->p_mode ? n * n * N : n * n, n * N, m * (N - 1),
-                             m * (N - 1), d->p_mode ? n * N : n};
-    void *hout[6] = {K, P, X, U, lin ? lin->d : nullptr, lin ? lin->p : nullptr};
-    for (int i = 0; i < nin; ++i)
-        if (!hin[i]) return set_err(i < 6 ? -(i + 2) : -8, "input pointer %d is NULL", i < 6 ? i + 2 : 8);
-    for (int i = 0; i < nout; ++i)
-        if (!hout[i]) return set_err(i < 4 ? -(i + 8 + o) : -8, "output pointer %d is NULL", i < 4 ? i + 8 + o : 8);
+    const size_t es = dsize(d->dtype);
     std::vector<Shard> sh = make_shards(d->batch, devices, ndev);
     const int64_t Bt = d->batch;
     const int lay = d->layout;
-    return run_shards(sh, info, Bt, [&](Shard &x) -> int {
+    return run_shards(sh, p.info, Bt, [&](Shard &x) -> int {
         ShardCtx c;
         hipError_t e = hipStreamCreateWithFlags(&c.s, hipStreamNonBlocking);
         if (e != hipSuccess) return hip_err(e, "hipStreamCreate");
-        void *din[9] = {}, *dout[6] = {}, *dinfo = nullptr;
+        DpTable td = t;
+        void *dinfo = nullptr;
         int r;
-        for (int i = 0; i < nin; ++i) {
-            if ((r = c.alloc(&din[i], szin[i] * es * x.nb))) return r;
-            if ((e = shard_h2d(din[i], hin[i], szin[i], es, x, Bt, lay, c.s)) != hipSuccess) return hip_err(e, "H2D");
+        for (int i = 0; i < t.nrows; ++i) {
+            const DpRow &h = t.row[i];
+            if ((r = c.alloc(&td.row[i].ptr, (size_t)h.elems * es * x.nb))) return r;
+            if (!h.out && (e = shard_h2d(td.row[i].ptr, h.ptr, h.elems, es, x, Bt, lay, c.s)) != hipSuccess)
+                return hip_err(e, "H2D");
         }
-        for (int i = 0; i < nout; ++i)
-            if ((r = c.alloc(&dout[i], szout[i] * es * x.nb))) return r;
         if ((r = c.alloc(&dinfo, 4 * x.nb))) return r;
         lqrx_dp_desc ds = *d;
         ds.batch = x.nb;
-        lqrx_dp_linear dl{};
-        if (lin) {
-            dl.q = din[6]; dl.r = din[7]; dl.qf = din[8]; dl.d = dout[4]; dl.p = dout[5];
-        }
-        if ((r = dp_solve_impl(&ds, din[0], din[1], din[2], din[3], din[4], din[5], lin ? &dl : nullptr, dout[0],
-                               dout[1], dout[2], dout[3], (int32_t *)dinfo, c.s)) < 0)
-            return r;
-        for (int i = 0; i < nout; ++i)
-            if ((e = shard_d2h(hout[i], dout[i], szout[i], es, x, Bt, lay, c.s)) != hipSuccess) return hip_err(e, "D2H");
-        if (info && (e = hipMemcpyAsync(info + x.b0, dinfo, 4 * x.nb, hipMemcpyDeviceToHost, c.s)) != hipSuccess)
+        if ((r = dp_run(&ds, td, (int32_t *)dinfo, c.s)) < 0) return r;
+        for (int i = 0; i < t.nrows; ++i)
+            if (t.row[i].out && (e = shard_d2h(t.row[i].ptr, td.row[i].ptr, t.row[i].elems, es, x, Bt, lay, c.s)) != hipSuccess)
+                return hip_err(e, "D2H");
+        if (p.info && (e = hipMemcpyAsync(p.info + x.b0, dinfo, 4 * x.nb, hipMemcpyDeviceToHost, c.s)) != hipSuccess)
             return hip_err(e, "D2H info");
         if ((e = hipStreamSynchronize(c.s)) != hipSuccess) return hip_err(e, "dp shard");
         return 0;
@@ -1465,7 +1423,8 @@ extern "C" int lqrx_dp_solve_host_devices(const lqrx_dp_desc *d, const void *A, 
                                           const void *R, const void *Qf, const void *x0, void *K, void *P, void *X,
                                           void *U, int32_t *info, const int32_t *devices, int32_t ndev)
 {
-    return dp_solve_host_devices_impl(d, A, B, Q, R, Qf, x0, nullptr, K, P, X, U, info, devices, ndev);
+    return dp_solve_host_devices_impl(d, DP_PLAIN, DpPtrs{A, B, nullptr, Q, R, nullptr, Qf, x0, nullptr, nullptr, K, P, X, U, info},
+                                      devices, ndev);
 }
 
 extern "C" int lqrx_dp_solve_linear_host_devices(const lqrx_dp_desc *d, const void *A, const void *B,
@@ -1473,8 +1432,8 @@ extern "C" int lqrx_dp_solve_linear_host_devices(const lqrx_dp_desc *d, const vo
                                                  const lqrx_dp_linear *lin, void *K, void *P, void *X, void *U,
                                                  int32_t *info, const int32_t *devices, int32_t ndev)
 {
-    if (!lin) return set_err(-8, "lin is NULL");
-    return dp_solve_host_devices_impl(d, A, B, Q, R, Qf, x0, lin, K, P, X, U, info, devices, ndev);
+    return dp_solve_host_devices_impl(d, DP_LINEAR, DpPtrs{A, B, nullptr, Q, R, nullptr, Qf, x0, lin, nullptr, K, P, X, U, info},
+                                      devices, ndev);
 }
 
 extern "C" int lqrx_kkt_solve_host_devices(const lqrx_kkt_desc *d, const void *Y, const void *y, const void *H,

@@ -88,6 +88,31 @@ class LsDesc(C.Structure):
 
 
 _VP = C.c_void_p
+
+# Argument order of every DP solve entry behind desc, by the parameter names of include/lqrx.h:
+# the five device entries, their _host twins (no stream) and the two _host_devices forms.
+_DP_SOLVE = {
+    "lqrx_dp_solve": "A B Q R Qf x0 K P X U info stream",
+    "lqrx_dp_solve_linear": "A B Q R Qf x0 lin K P X U info stream",
+    "lqrx_dp_solve_affine": "A B c Q R Qf x0 lin K P X U info stream",
+    "lqrx_dp_solve_cross": "A B c Q R M Qf x0 lin K P X U info stream",
+    "lqrx_dp_solve_value": "A B c Q R M Qf x0 lin val K P X U info stream",
+}
+DP_ENTRY_ARGS = {}
+for _name, _order in _DP_SOLVE.items():
+    DP_ENTRY_ARGS[_name] = tuple(_order.split())
+    DP_ENTRY_ARGS[_name + "_host"] = DP_ENTRY_ARGS[_name][:-1]
+for _name in ("lqrx_dp_solve", "lqrx_dp_solve_linear"):
+    DP_ENTRY_ARGS[_name + "_host_devices"] = DP_ENTRY_ARGS[_name + "_host"] + ("devices", "ndev")
+_DP_ARGTYPES = {"lin": C.POINTER(DpLinear), "val": C.POINTER(DpValue), "ndev": C.c_int32}
+
+
+def dp_call(entry: str, desc: DpDesc, args: dict) -> int:
+    """Call the DP solve entry `entry` with its arguments taken by name from `args` (ctypes values;
+    names `entry` does not take are ignored) and laid out in the entry's order."""
+    return getattr(load(), entry)(C.byref(desc), *[args[k] for k in DP_ENTRY_ARGS[entry]])
+
+
 _SIGS = {
     "lqrx_abi_version": (C.c_int, []),
     "lqrx_build_info": (C.c_char_p, []),
@@ -95,33 +120,14 @@ _SIGS = {
     "lqrx_get_last_error": (C.c_int, [C.c_char_p, C.c_size_t]),
     "lqrx_device_available": (C.c_int, []),
     "lqrx_scratch_trim": (C.c_int, [C.c_int32, C.c_size_t]),
-    "lqrx_dp_solve": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 10 + [_VP, _VP]),
-    "lqrx_dp_solve_host": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 10 + [_VP]),
+    **{name: (C.c_int, [C.POINTER(DpDesc)] + [_DP_ARGTYPES.get(k, _VP) for k in order])
+       for name, order in DP_ENTRY_ARGS.items()},
     "lqrx_dp_compute_ctg": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 8 + [_VP]),
     "lqrx_dp_compute_ctg_host": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 8),
-    "lqrx_dp_solve_linear": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 6 + [C.POINTER(DpLinear)]
-                             + [_VP] * 4 + [_VP, _VP]),
-    "lqrx_dp_solve_linear_host": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 6
-                                  + [C.POINTER(DpLinear)] + [_VP] * 5),
-    "lqrx_dp_solve_affine": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 7 + [C.POINTER(DpLinear)]
-                             + [_VP] * 4 + [_VP, _VP]),
-    "lqrx_dp_solve_affine_host": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 7
-                                  + [C.POINTER(DpLinear)] + [_VP] * 5),
-    "lqrx_dp_solve_cross": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 8 + [C.POINTER(DpLinear)]
-                            + [_VP] * 4 + [_VP, _VP]),
-    "lqrx_dp_solve_cross_host": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 8
-                                 + [C.POINTER(DpLinear)] + [_VP] * 5),
-    "lqrx_dp_solve_value": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 8 + [C.POINTER(DpLinear)]
-                            + [C.POINTER(DpValue)] + [_VP] * 4 + [_VP, _VP]),
-    "lqrx_dp_solve_value_host": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 8
-                                 + [C.POINTER(DpLinear)] + [C.POINTER(DpValue)] + [_VP] * 5),
     "lqrx_dp_costates": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 13 + [_VP]),
     "lqrx_dp_costates_host": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 13),
     "lqrx_dp_solve_adjoint": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 9 + [C.POINTER(DpGrad)]
                               + [_VP, _VP]),
-    "lqrx_dp_solve_host_devices": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 10 + [_VP, _VP, C.c_int32]),
-    "lqrx_dp_solve_linear_host_devices": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 6 + [C.POINTER(DpLinear)]
-                                          + [_VP] * 5 + [_VP, C.c_int32]),
     "lqrx_kkt_solve_host_devices": (C.c_int, [C.POINTER(KktDesc)] + [_VP] * 7 + [_VP, C.c_int32]),
     "lqrx_kkt_solve": (C.c_int, [C.POINTER(KktDesc)] + [_VP] * 7 + [_VP]),
     "lqrx_kkt_solve_host": (C.c_int, [C.POINTER(KktDesc)] + [_VP] * 7),

@@ -22,7 +22,7 @@ Every compute call goes through liblqrx.so — there is no CPU fallback.
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 
 import numpy as np
 
@@ -214,6 +214,10 @@ def _devices(devices):
     return dv, dv.ctypes.data_as(C.c_void_p), C.c_int32(len(dv))
 
 
+# the entry kinds past linear have no devices= form: kind → what the ValueError names
+_DP_NO_DEVICES = {"value": "value=True", "cross": "a cost cross term M", "affine": "an affine offset c"}
+
+
 def solve_batch(b: LQRBatch, dtype: int = _lib.F64, all_P: bool = False, layout: int = 0,
                 devices=None, value: bool = False, costates: bool = False):
     """Batched solve! through lqrx_dp_solve_host.  Returns dict of logical arrays
@@ -234,122 +238,70 @@ def solve_batch(b: LQRBatch, dtype: int = _lib.F64, all_P: bool = False, layout:
     bt = b.batch
     tvAB, tvQR = b.time_varying()
     npdt = np.float64 if dtype == _lib.F64 else np.float32
-    if value:
+    kab, kq, kP = (N - 1 if tvAB else 1), (N - 1 if tvQR else 1), (N if all_P else 1)
+    kind = ("value" if value else "cross" if b.M is not None else "affine" if b.c is not None
+            else "linear" if b.q is not None else "")
+    if kind in _DP_NO_DEVICES:
         if devices is not None:
-            raise ValueError("devices= is not available with value=True")
-        if b.M is None:
-            b = LQRBatch(b.A, b.B, b.Q, b.R, b.Qf, b.x0, b.N, b.extra, q=b.q, r=b.r, qf=b.qf, c=b.c,
-                         M=np.zeros((bt, N - 1, m, n) if tvQR else (bt, m, n), npdt))
-    cross = b.M is not None
-    aff = b.c is not None or cross
-    if cross:
-        if devices is not None:
-            raise ValueError("devices= is not available with a cost cross term M")
-        if np.shape(b.M)[-2:] != (m, n):
-            raise ValueError("M is (m, n) per trajectory (per knot), the shape of K")
-        if (np.ndim(b.M) == 4) != bool(tvQR):
-            raise ValueError("M carries a knot axis (batch, N-1, m, n) exactly when Q and R carry one")
-        if b.c is None:
-            b = LQRBatch(b.A, b.B, b.Q, b.R, b.Qf, b.x0, b.N, b.extra, q=b.q, r=b.r, qf=b.qf,
-                         c=np.zeros((bt, N - 1, n) if tvAB else (bt, n), npdt), M=b.M)
-    if aff:
-        if devices is not None:
-            raise ValueError("devices= is not available with an affine offset c")
+            raise ValueError("devices= is not available with " + _DP_NO_DEVICES[kind])
+        # missing c, M, q, r, qf are zeros, with a knot axis where their neighbours carry one
+        ab, qr = ((N - 1,) if tvAB else ()), ((N - 1,) if tvQR else ())
+        fill = dict(c=(bt, *ab, n), q=(bt, *qr, n), r=(bt, *qr, m), qf=(bt, n))
+        if kind != "affine":
+            fill["M"] = (bt, *qr, m, n)
+        b = replace(b, **{k: np.zeros(sh, npdt) for k, sh in fill.items() if getattr(b, k) is None})
+        if b.M is not None:
+            if np.shape(b.M)[-2:] != (m, n):
+                raise ValueError("M is (m, n) per trajectory (per knot), the shape of K")
+            if (np.ndim(b.M) == 4) != bool(tvQR):
+                raise ValueError("M carries a knot axis (batch, N-1, m, n) exactly when Q and R carry one")
         if (np.ndim(b.c) == 3) != bool(tvAB):
             raise ValueError("c carries a knot axis (batch, N-1, n) exactly when A and B carry one")
-        kq = N - 1 if tvQR else 1
-        zeros = lambda *s: np.zeros(s, npdt)
-        b = LQRBatch(b.A, b.B, b.Q, b.R, b.Qf, b.x0, b.N, b.extra,
-                     q=b.q if b.q is not None else (zeros(bt, kq, n) if tvQR else zeros(bt, n)),
-                     r=b.r if b.r is not None else (zeros(bt, kq, m) if tvQR else zeros(bt, m)),
-                     qf=b.qf if b.qf is not None else zeros(bt, n), c=b.c, M=b.M)
-    lib = _lib.load()
-    ins = [to_abi(np.asarray(x, dtype=npdt)) for x in (b.A, b.B, b.Q, b.R, b.Qf)]
-    ins0 = ins   # layout 0, for the costate sweep
-    x0 = np.ascontiguousarray(np.asarray(b.x0, dtype=npdt))
-    if layout == 1:
-        ins = [to_soa(a, bt) for a in ins]
-        x0 = to_soa(x0, bt)
-    K = np.zeros(bt * (N - 1) * m * n, npdt)
-    P = np.zeros(bt * n * n * (N if all_P else 1), npdt)
-    X = np.zeros(bt * N * n, npdt)
-    U = np.zeros(bt * (N - 1) * m, npdt)
-    info = np.zeros(bt, np.int32)
-    d = _lib.DpDesc(n, m, N, dtype, bt, layout, 1 if all_P else 0, tvAB, tvQR)
-    lin = b.q is not None
-    if lin:   # linear cost terms: lqrx_dp_solve_linear_host
-        if b.r is None or b.qf is None:
-            raise ValueError("linear cost terms need q, r and qf together")
-        kq = N - 1 if tvQR else 1
-        vec = lambda a, w: np.ascontiguousarray(np.asarray(a, dtype=npdt).reshape(bt * kq * w))
-        q, r = vec(b.q, n), vec(b.r, m)
-        qf = np.ascontiguousarray(np.asarray(b.qf, dtype=npdt).reshape(bt * n))
-        if layout == 1:
-            q, r, qf = to_soa(q, bt), to_soa(r, bt), to_soa(qf, bt)
-        dff = np.zeros(bt * (N - 1) * m, npdt)
-        pv = np.zeros(bt * n * (N if all_P else 1), npdt)
-        ln = _lib.DpLinear(_ptr(q).value, _ptr(r).value, _ptr(qf).value, _ptr(dff).value,
-                           _ptr(pv).value)
-        args = (C.byref(d), *[_ptr(a) for a in ins], _ptr(x0), C.byref(ln), _ptr(K), _ptr(P),
-                _ptr(X), _ptr(U), _ptr(info))
-        if aff:   # c follows A and B: argument 4
-            cv = np.ascontiguousarray(np.asarray(b.c, dtype=npdt).reshape(bt * (N - 1 if tvAB else 1) * n))
-            if layout == 1:
-                cv = to_soa(cv, bt)
-            if cross:   # M follows Q and R: argument 7
-                Mv = to_abi(np.asarray(b.M, dtype=npdt)).reshape(-1)
-                if layout == 1:
-                    Mv = to_soa(Mv, bt)
-                if value:   # val follows lin: argument 11
-                    sv = np.zeros(bt * (N if all_P else 1), npdt)
-                    dVv, Jv = np.zeros(bt, npdt), np.zeros(bt, npdt)
-                    vl = _lib.DpValue(_ptr(sv).value, _ptr(dVv).value, _ptr(Jv).value)
-                    rc = _lib.check(lib.lqrx_dp_solve_value_host(*args[:3], _ptr(cv), *args[3:5], _ptr(Mv),
-                                                                 *args[5:8], C.byref(vl), *args[8:]))
-                else:
-                    rc = _lib.check(lib.lqrx_dp_solve_cross_host(*args[:3], _ptr(cv), *args[3:5], _ptr(Mv),
-                                                                 *args[5:]))
-            else:
-                rc = _lib.check(lib.lqrx_dp_solve_affine_host(*args[:3], _ptr(cv), *args[3:]))
-        elif devices is None:
-            rc = _lib.check(lib.lqrx_dp_solve_linear_host(*args))
-        else:
-            dv, dp_, nd = _devices(devices)
-            rc = _lib.check(lib.lqrx_dp_solve_linear_host_devices(*args, dp_, nd))
-    else:
-        args = (C.byref(d), *[_ptr(a) for a in ins], _ptr(x0), _ptr(K), _ptr(P), _ptr(X), _ptr(U),
-                _ptr(info))
-        if devices is None:
-            rc = _lib.check(lib.lqrx_dp_solve_host(*args))
-        else:
-            dv, dp_, nd = _devices(devices)
-            rc = _lib.check(lib.lqrx_dp_solve_host_devices(*args, dp_, nd))
-    if layout == 1:
-        K, P, X, U = (from_soa(a, bt) for a in (K, P, X, U))
-        if lin:
-            dff, pv = from_soa(dff, bt), from_soa(pv, bt)
-        if value and all_P:
-            sv = from_soa(sv, bt)
-    out = dict(K=from_abi(K, (bt, N - 1, m, n)),
-               P=from_abi(P, (bt, N, n, n) if all_P else (bt, n, n)),
-               X=X.reshape(bt, N, n), U=U.reshape(bt, N - 1, m), info=info, rc=rc)
-    if lin:
-        out["d"] = dff.reshape(bt, N - 1, m)
-        out["p"] = pv.reshape(bt, N, n) if all_P else pv.reshape(bt, n)
+    elif kind == "linear" and (b.r is None or b.qf is None):
+        raise ValueError("linear cost terms need q, r and qf together")
+    # the entry's inputs by name, flat and in layout 0: matrices column-major, vectors as they are
+    mats = ("A", "B", "Q", "R", "Qf") + (("M",) if b.M is not None else ())
+    vecs = dict(x0=bt * n, **(dict(q=bt * kq * n, r=bt * kq * m, qf=bt * n) if kind else {}),
+                **(dict(c=bt * kab * n) if b.c is not None else {}))
+    in0 = {k: to_abi(np.asarray(getattr(b, k), dtype=npdt)).reshape(-1) for k in mats}
+    in0.update({k: np.ascontiguousarray(np.asarray(getattr(b, k), dtype=npdt).reshape(sz)) for k, sz in vecs.items()})
+    outs = dict(K=bt * (N - 1) * m * n, P=bt * n * n * kP, X=bt * N * n, U=bt * (N - 1) * m)
+    if kind:
+        outs.update(d=bt * (N - 1) * m, p=bt * n * kP)
     if value:
-        out["s"] = sv.reshape(bt, N) if all_P else sv
-        out["dV"], out["J"] = dVv, Jv
+        outs.update(s=bt * kP, dV=bt, J=bt)
+    buf = {k: to_soa(a, bt) for k, a in in0.items()} if layout == 1 else dict(in0)
+    buf.update({k: np.zeros(sz, npdt) for k, sz in outs.items()})
+    buf["info"] = np.zeros(bt, np.int32)
+    args = {k: _ptr(a) for k, a in buf.items()}
+    if kind:
+        ln = _lib.DpLinear(*[args[k].value for k in ("q", "r", "qf", "d", "p")])
+        args["lin"] = C.byref(ln)
+    if value:
+        vl = _lib.DpValue(*[args[k].value for k in ("s", "dV", "J")])
+        args["val"] = C.byref(vl)
+    if devices is not None:
+        dv, args["devices"], args["ndev"] = _devices(devices)
+    entry = "lqrx_dp_solve" + ("_" + kind if kind else "") + ("_host" if devices is None else "_host_devices")
+    d = _lib.DpDesc(n, m, N, dtype, bt, layout, 1 if all_P else 0, tvAB, tvQR)
+    rc = _lib.check(_lib.dp_call(entry, d, args))
+    o = {k: from_soa(buf[k], bt) if layout == 1 else buf[k] for k in outs}
+    out = dict(K=from_abi(o["K"], (bt, N - 1, m, n)),
+               P=from_abi(o["P"], (bt, N, n, n) if all_P else (bt, n, n)),
+               X=o["X"].reshape(bt, N, n), U=o["U"].reshape(bt, N - 1, m), info=buf["info"], rc=rc)
+    if kind:
+        out["d"] = o["d"].reshape(bt, N - 1, m)
+        out["p"] = o["p"].reshape(bt, N, n) if all_P else o["p"].reshape(bt, n)
+    if value:
+        out["s"] = o["s"].reshape(bt, N) if all_P else o["s"]
+        out["dV"], out["J"] = o["dV"], o["J"]
     if costates:   # λ_k from the K, X, U just returned; absent M, q, r, qf are NULL (zero)
-        flat = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a, dtype=npdt)).reshape(-1)
-        Mc = to_abi(np.asarray(b.M, dtype=npdt)).reshape(-1) if cross else None
-        qc, rc_, qfc = flat(b.q), flat(b.r), flat(b.qf)
-        Kc = to_abi(out["K"]).reshape(-1)
-        Xc, Uc = flat(out["X"]), flat(out["U"])
+        cin = dict(in0, K=to_abi(out["K"]).reshape(-1), X=o["X"], U=o["U"])
         lam = np.zeros(bt * N * n, npdt)
         d0 = _lib.DpDesc(n, m, N, dtype, bt, 0, 0, tvAB, tvQR)
-        op = lambda a: None if a is None else _ptr(a)
-        _lib.check(lib.lqrx_dp_costates_host(C.byref(d0), *[_ptr(a) for a in ins0[:4]], op(Mc), _ptr(ins0[4]),
-                                             op(qc), op(rc_), op(qfc), _ptr(Kc), _ptr(Xc), _ptr(Uc), _ptr(lam)))
+        _lib.check(_lib.load().lqrx_dp_costates_host(
+            C.byref(d0), *[_ptr(cin[k]) if k in cin else None
+                           for k in ("A", "B", "Q", "R", "M", "Qf", "q", "r", "qf", "K", "X", "U")], _ptr(lam)))
         out["lam"] = lam.reshape(bt, N, n)
     return out
 
@@ -469,60 +421,43 @@ def dp_solve_device(t: dict, N: int, p_mode: int = 0, stream: int | None = None,
     tdt = t["A"].dtype
     dtype = _lib.F64 if tdt == torch.float64 else _lib.F32
     dev = t["A"].device
-    if out is None:
-        out = dict(K=torch.empty(bt * (N - 1) * m * n, dtype=tdt, device=dev),
-                   P=torch.empty(bt * n * n * (N if p_mode else 1), dtype=tdt, device=dev),
-                   X=torch.empty(bt * N * n, dtype=tdt, device=dev),
-                   U=torch.empty(bt * (N - 1) * m, dtype=tdt, device=dev),
-                   info=torch.empty(bt, dtype=torch.int32, device=dev))
+    has = lambda k: t.get(k) is not None
+    if has("c") and not has("q"):
+        raise ValueError("dp_solve_device: c needs q, r, qf (zeros for a problem without cost terms)")
+    if has("M") and not has("c"):
+        raise ValueError("dp_solve_device: M needs c and q, r, qf (zeros where the problem has none)")
+    if value and not has("M"):
+        raise ValueError("dp_solve_device: value=True needs M, c and q, r, qf (zeros where the problem has none)")
+    kind = "value" if value else "cross" if has("M") else "affine" if has("c") else "linear" if has("q") else ""
+    entry = "lqrx_dp_solve" + ("_" + kind if kind else "")
+    kP = N if p_mode else 1
+    # outputs the caller's `out` does not hold yet, group by group (elements; info is int32)
+    groups = [dict(K=bt * (N - 1) * m * n, P=bt * n * n * kP, X=bt * N * n, U=bt * (N - 1) * m, info=bt)]
+    if kind:
+        groups.append(dict(d=bt * (N - 1) * m, p=bt * n * kP))
+    if value:
+        groups.append(dict(s=bt * kP, dV=bt, J=bt))
+    out = {} if out is None else out
+    for g in groups:
+        if next(iter(g)) not in out:
+            out.update({k: torch.empty(sz, dtype=torch.int32 if k == "info" else tdt, device=dev) for k, sz in g.items()})
     d = _lib.DpDesc(n, m, N, dtype, bt, layout, p_mode, int(t.get("tv_AB", 0)), int(t.get("tv_QR", 0)))
     p = lambda x: C.c_void_p(x.data_ptr())
     st = C.c_void_p(stream) if stream else None
-    if t.get("c") is not None and t.get("q") is None:
-        raise ValueError("dp_solve_device: c needs q, r, qf (zeros for a problem without cost terms)")
-    if t.get("M") is not None and t.get("c") is None:
-        raise ValueError("dp_solve_device: M needs c and q, r, qf (zeros where the problem has none)")
-    if value and t.get("M") is None:
-        raise ValueError("dp_solve_device: value=True needs M, c and q, r, qf (zeros where the problem has none)")
-    if t.get("q") is not None:
-        if "d" not in out:
-            out["d"] = torch.empty(bt * (N - 1) * m, dtype=tdt, device=dev)
-            out["p"] = torch.empty(bt * n * (N if p_mode else 1), dtype=tdt, device=dev)
-        ln = _lib.DpLinear(t["q"].data_ptr(), t["r"].data_ptr(), t["qf"].data_ptr(),
-                           out["d"].data_ptr(), out["p"].data_ptr())
-        if value:
-            if "s" not in out:
-                out["s"] = torch.empty(bt * (N if p_mode else 1), dtype=tdt, device=dev)
-                out["dV"] = torch.empty(bt, dtype=tdt, device=dev)
-                out["J"] = torch.empty(bt, dtype=tdt, device=dev)
-            opt = lambda k: out[k].data_ptr() if out.get(k) is not None else None   # dV, J: optional
-            vl = _lib.DpValue(out["s"].data_ptr(), opt("dV"), opt("J"))
-            rc = lib.lqrx_dp_solve_value(C.byref(d), p(t["A"]), p(t["B"]), p(t["c"]), p(t["Q"]),
-                                         p(t["R"]), p(t["M"]), p(t["Qf"]), p(t["x0"]), C.byref(ln),
-                                         C.byref(vl), p(out["K"]), p(out["P"]), p(out["X"]),
-                                         p(out["U"]), p(out["info"]), st)
-        elif t.get("M") is not None:
-            rc = lib.lqrx_dp_solve_cross(C.byref(d), p(t["A"]), p(t["B"]), p(t["c"]), p(t["Q"]),
-                                         p(t["R"]), p(t["M"]), p(t["Qf"]), p(t["x0"]), C.byref(ln),
-                                         p(out["K"]), p(out["P"]), p(out["X"]), p(out["U"]),
-                                         p(out["info"]), st)
-        elif t.get("c") is not None:
-            rc = lib.lqrx_dp_solve_affine(C.byref(d), p(t["A"]), p(t["B"]), p(t["c"]), p(t["Q"]),
-                                          p(t["R"]), p(t["Qf"]), p(t["x0"]), C.byref(ln), p(out["K"]),
-                                          p(out["P"]), p(out["X"]), p(out["U"]), p(out["info"]), st)
-        else:
-            rc = lib.lqrx_dp_solve_linear(C.byref(d), p(t["A"]), p(t["B"]), p(t["Q"]), p(t["R"]),
-                                          p(t["Qf"]), p(t["x0"]), C.byref(ln), p(out["K"]),
-                                          p(out["P"]), p(out["X"]), p(out["U"]), p(out["info"]), st)
-    else:
-        rc = lib.lqrx_dp_solve(C.byref(d), p(t["A"]), p(t["B"]), p(t["Q"]), p(t["R"]), p(t["Qf"]),
-                               p(t["x0"]), p(out["K"]), p(out["P"]), p(out["X"]), p(out["U"]),
-                               p(out["info"]), st)
-    _lib.check(rc)
+    tensor = lambda k: out[k] if k in out else t[k]      # input and output names are disjoint
+    args = {k: p(tensor(k)) for k in _lib.DP_ENTRY_ARGS[entry] if k not in ("lin", "val", "stream")}
+    args["stream"] = st
+    if kind:
+        ln = _lib.DpLinear(*[tensor(k).data_ptr() for k in ("q", "r", "qf", "d", "p")])
+        args["lin"] = C.byref(ln)
+    if value:   # dV, J: optional, NULL where `out` holds None (or nothing) for them
+        vl = _lib.DpValue(*[out[k].data_ptr() if out.get(k) is not None else None for k in ("s", "dV", "J")])
+        args["val"] = C.byref(vl)
+    rc = _lib.check(_lib.dp_call(entry, d, args))
     if costates:
         if out.get("lam") is None:
             out["lam"] = torch.empty(bt * N * n, dtype=tdt, device=dev)
-        opt = lambda k: p(t[k]) if t.get(k) is not None else None
+        opt = lambda k: p(t[k]) if has(k) else None
         _lib.check(lib.lqrx_dp_costates(C.byref(d), p(t["A"]), p(t["B"]), p(t["Q"]), p(t["R"]), opt("M"),
                                         p(t["Qf"]), opt("q"), opt("r"), opt("qf"), p(out["K"]), p(out["X"]),
                                         p(out["U"]), p(out["lam"]), st))

@@ -509,7 +509,7 @@ int lqrx_kkt_solve_host_devices(const lqrx_kkt_desc *desc, const void *Y, const 
  *          (the KKT δz order)
  *   x0, xf nx·batch
  *   lam    (nx(N+1) + stage_rows(N−2))·batch out: multipliers of the last accepted Newton
- *          step (KKT λ order)
+ *          step (KKT λ order); unspecified for a trajectory with iters = 0 (no step accepted)
  *   iters  int32·batch out: accepted steps
  *   status int32·batch out: 0 converged (‖c‖∞ < tol_p and ‖∇f+∇cᵀλ‖₂ < tol_d before a
  *          step), 1 max_iters reached, 2 line search failed (iterate left unchanged)

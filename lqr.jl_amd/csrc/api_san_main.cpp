@@ -9,6 +9,7 @@
 // buffer truncation.  With no device the device-touching paths must fail cleanly with
 // LQRX_ERR_HIP / LQRX_ERR_NODEVICE rather than touch memory they do not own.
 #include "../../include/lqrx.h"
+#include "lqrx_internal.h"
 
 #include <cmath>
 #include <cstddef>
@@ -128,6 +129,13 @@ int main()
 {
     CHECK(lqrx_abi_version() == LQRX_ABI_VERSION);
     const int have_gpu = lqrx_device_available();
+    // dp_kind() on the 16 combinations of lin / aff / cross / value: the five nested ones (bits =
+    // 2^k − 1) are the kinds 0 … 4, every other one is −1 (dp_launch then refuses it)
+    for (int bits = 0; bits < 16; ++bits) {
+        lqrx::DpArgs a{};
+        a.lin = bits & 1; a.aff = bits >> 1 & 1; a.cross = bits >> 2 & 1; a.value = bits >> 3 & 1;
+        CHECK(lqrx::dp_kind(a) == (bits == 0 ? 0 : bits == 1 ? 1 : bits == 3 ? 2 : bits == 7 ? 3 : bits == 15 ? 4 : -1));
+    }
 
     // ---- DP validation ----
     double dummy[64] = {0};

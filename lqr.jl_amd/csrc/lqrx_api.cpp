@@ -146,8 +146,8 @@ hipError_t scratch_trim(int device, size_t keep)
 
 namespace {
 // ---- the DP solve entries: one table of a call's buffers ----
-// The entry kinds nest: each adds arguments to the one before it (lin; c; M; val).
-enum DpKind { DP_PLAIN, DP_LINEAR, DP_AFFINE, DP_CROSS, DP_VALUE };
+// The entry kinds (enum DpKind, lqrx_internal.h) nest: each adds arguments to the one before it.
+using lqrx::DpKind, lqrx::DP_PLAIN, lqrx::DP_LINEAR, lqrx::DP_AFFINE, lqrx::DP_CROSS, lqrx::DP_VALUE;
 
 // the caller's pointers, whatever the entry's argument order
 struct DpPtrs {

@@ -1779,12 +1779,18 @@ template <int MT>
 static hipError_t launch_wg4(const DpArgs &a, hipStream_t s)
 {
     dim3 grid((unsigned)a.batch), block(256);
-    const bool tv = a.tv_AB || a.tv_QR;
-    if (a.lin && tv) hipLaunchKernelGGL((dp_wg4_kernel<double, MT, VAR_TV | VAR_LIN>), grid, block, 0, s, a);
-    else if (a.lin) hipLaunchKernelGGL((dp_wg4_kernel<double, MT, VAR_LIN>), grid, block, 0, s, a);
-    else if (tv) hipLaunchKernelGGL((dp_wg4_kernel<double, MT, VAR_TV>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((dp_wg4_kernel<double, MT, 0>), grid, block, 0, s, a);
-    return hipGetLastError();
+    return with_bools(a.lin, a.tv_AB || a.tv_QR, [&](auto lin, auto tv) {
+        constexpr int VAR = (decltype(lin)::value ? VAR_LIN : 0) | (decltype(tv)::value ? VAR_TV : 0);
+        hipLaunchKernelGGL((dp_wg4_kernel<double, MT, VAR>), grid, block, 0, s, a);
+        return hipGetLastError();
+    });
+}
+
+// the VAR bits of a solve kind (enum DpKind): each kind carries the bits of the kinds below it
+constexpr int var_of(int kind)
+{
+    return (kind >= DP_LINEAR ? VAR_LIN : 0) | (kind >= DP_AFFINE ? VAR_AFF : 0) | (kind >= DP_CROSS ? VAR_CROSS : 0) |
+           (kind >= DP_VALUE ? VAR_VALUE : 0);
 }
 
 // ------------------------------------------------------------------ launcher
@@ -1798,7 +1804,7 @@ static hipError_t launch_dp(const DpArgs &a, hipStream_t s);
 //   2×2                     2                   1        1
 //   4×2                     1                   1        1
 template <typename T, int NT, int MT>
-static hipError_t launch_dp_tv(const DpArgs &a, hipStream_t s)
+static hipError_t launch_dp_tv(const DpArgs &a, int kind, hipStream_t s)
 {
     // time-invariant (plain, linear terms, affine offset): 2 waves/SIMD up to n ≤ 32, 1 at n ≤ 64.
     // 2×2 fp64 tiles do not fit 256 registers (≈ 450 live): the 2-wave launch bound compiles
@@ -1815,30 +1821,24 @@ static hipError_t launch_dp_tv(const DpArgs &a, hipStream_t s)
     // 1×1 (double) and up to 2×1 (float) grids; time-invariant LIN keeps the plain kernel's
     // occupancy (its vector work sits after the solve, where fewer tiles are live)
     constexpr int LW = (NT * MT <= (sizeof(T) == 4 ? 2 : 1)) ? 2 : 1;
-    // value-function constant (needs lin, aff and cross): the launch bounds of the cross variants
-    if (a.value && (a.tv_AB || a.tv_QR))
-        return launch_dp<T, NT, MT, LW, VAR_TV | VAR_LIN | VAR_AFF | VAR_CROSS | VAR_VALUE>(a, s);
-    if (a.value) return launch_dp<T, NT, MT, WAVES, VAR_LIN | VAR_AFF | VAR_CROSS | VAR_VALUE>(a, s);
-    if (a.cross && (a.tv_AB || a.tv_QR)) return launch_dp<T, NT, MT, LW, VAR_TV | VAR_LIN | VAR_AFF | VAR_CROSS>(a, s);
-    if (a.cross) return launch_dp<T, NT, MT, WAVES, VAR_LIN | VAR_AFF | VAR_CROSS>(a, s);
-    // affine offset (needs lin): the launch bounds of the linear-terms variants
-    if (a.aff && (a.tv_AB || a.tv_QR)) return launch_dp<T, NT, MT, LW, VAR_TV | VAR_LIN | VAR_AFF>(a, s);
-    if (a.aff) return launch_dp<T, NT, MT, WAVES, VAR_LIN | VAR_AFF>(a, s);
-    if (a.lin && (a.tv_AB || a.tv_QR)) return launch_dp<T, NT, MT, LW, VAR_TV | VAR_LIN>(a, s);
-    if (a.lin) return launch_dp<T, NT, MT, WAVES, VAR_LIN>(a, s);
-    if (a.tv_AB || a.tv_QR) return launch_dp<T, NT, MT, TVW, VAR_TV | LQRX_DP_TVEXTRA>(a, s);
-    return launch_dp<T, NT, MT, WAVES, 0>(a, s);
+    // (the affine offset, the cross term and the value constant keep the linear-terms launch bounds)
+    return with_kind(kind, [&](auto k) {
+        return with_bool(a.tv_AB || a.tv_QR, [&](auto tv) {
+            constexpr int KIND = decltype(k)::value, TV = decltype(tv)::value;
+            constexpr int VAR = var_of(KIND) | (TV ? VAR_TV | (KIND == DP_PLAIN ? LQRX_DP_TVEXTRA : 0) : 0);
+            return launch_dp<T, NT, MT, !TV ? WAVES : (KIND == DP_PLAIN ? TVW : LW), VAR>(a, s);
+        });
+    });
 }
 
 template <typename T, int NT, int MT, int WAVES, int VAR>
 static hipError_t launch_dp(const DpArgs &a, hipStream_t s)
 {
     dim3 grid((unsigned)a.batch), block(64);
-    if (a.n == NT * 16 && a.m == MT * 16)
-        hipLaunchKernelGGL((dp_riccati_kernel<T, NT, MT, WAVES, VAR, true>), grid, block, 0, s, a);
-    else
-        hipLaunchKernelGGL((dp_riccati_kernel<T, NT, MT, WAVES, VAR, false>), grid, block, 0, s, a);
-    return hipGetLastError();
+    return with_bool(a.n == NT * 16 && a.m == MT * 16, [&](auto full) {
+        hipLaunchKernelGGL((dp_riccati_kernel<T, NT, MT, WAVES, VAR, decltype(full)::value>), grid, block, 0, s, a);
+        return hipGetLastError();
+    });
 }
 
 hipError_t dp_launch(const DpArgs &a_in, hipStream_t s)
@@ -1846,33 +1846,32 @@ hipError_t dp_launch(const DpArgs &a_in, hipStream_t s)
     static const int ns_off = [] { const char *e = std::getenv("LQRX_DP_NS_OFF"); return e && *e == '1' ? 1 : 0; }();
     DpArgs a = a_in;
     a.ns_off = ns_off;
+    const int kind = dp_kind(a);   // the one check that the flags nest; the launchers take the kind
+    if (kind < 0) return hipErrorInvalidValue;
     // n ≤ 4: one lane per trajectory (a 16×16 MFMA tile would be mostly padding)
-    if (dp_lane_supported(a.n, a.m)) return dp_lane_launch(a, s);
+    if (dp_lane_supported(a.n, a.m)) return dp_lane_launch(a, kind, s);
     // smallest instantiated tile grid that covers (n, m); padding is exact (zero rows /
     // columns, unit diagonal in R), see tiles_load
     const int nt = (a.n + 15) / 16, mt = (a.m + 15) / 16;
     // LQRX_DP_BIG=1 sends every shape past the lane kernel to dp_big_kernel (A/B checks)
     static const bool force_big = [] { const char *e = std::getenv("LQRX_DP_BIG"); return e && *e == '1'; }();
     if (force_big && dp_big_supported(a.n, a.m)) return dp_big_launch(a, s);
-    if (a.dtype == 0) {
-        if (nt <= 1 && mt <= 1) return launch_dp_tv<double, 1, 1>(a, s);
-        if (nt <= 2 && mt <= 1) return launch_dp_tv<double, 2, 1>(a, s);
-        if (nt <= 2 && mt <= 2) return launch_dp_tv<double, 2, 2>(a, s);
-        // n = 64, m ∈ {16, 32}: four waves per trajectory — time-invariant or time-varying, with
-        // or without linear terms (LQRX_DP_WG4=0 in the environment: the one-wave kernel, for A/B
-        // runs and tests)
-        static const bool wg4 = [] { const char *e = std::getenv("LQRX_DP_WG4"); return !(e && *e == '0'); }();
+    // fp64, n = 64, m ∈ {16, 32}: four waves per trajectory — time-invariant or time-varying, with
+    // or without linear terms (LQRX_DP_WG4=0 in the environment: the one-wave kernel, for A/B
+    // runs and tests)
+    static const bool wg4 = [] { const char *e = std::getenv("LQRX_DP_WG4"); return !(e && *e == '0'); }();
+    return with_dtype(a.dtype, [&](auto t) {
+        using T = decltype(t);
+        if (nt <= 1 && mt <= 1) return launch_dp_tv<T, 1, 1>(a, kind, s);
+        if (nt <= 2 && mt <= 1) return launch_dp_tv<T, 2, 1>(a, kind, s);
+        if (nt <= 2 && mt <= 2) return launch_dp_tv<T, 2, 2>(a, kind, s);
         // (an affine or cross call takes the one-wave kernel below: dp_wg4_kernel has no c_k, no M_k)
-        if (wg4 && !a.aff && a.n == 64 && (a.m == 16 || a.m == 32))
-            return a.m == 16 ? launch_wg4<1>(a, s) : launch_wg4<2>(a, s);
-        if (nt <= 4 && mt <= 2) return launch_dp_tv<double, 4, 2>(a, s);
-    } else {
-        if (nt <= 1 && mt <= 1) return launch_dp_tv<float, 1, 1>(a, s);
-        if (nt <= 2 && mt <= 1) return launch_dp_tv<float, 2, 1>(a, s);
-        if (nt <= 2 && mt <= 2) return launch_dp_tv<float, 2, 2>(a, s);
-        if (nt <= 4 && mt <= 2) return launch_dp_tv<float, 4, 2>(a, s);    // cfg5: n=64 m=32
-    }
-    return dp_big_launch(a, s);     // past the register tiles: workgroup per trajectory
+        if constexpr (std::is_same_v<T, double>)
+            if (wg4 && kind <= DP_LINEAR && a.n == 64 && (a.m == 16 || a.m == 32))
+                return a.m == 16 ? launch_wg4<1>(a, s) : launch_wg4<2>(a, s);
+        if (nt <= 4 && mt <= 2) return launch_dp_tv<T, 4, 2>(a, kind, s);    // cfg5: n=64 m=32
+        return dp_big_launch(a, s);     // past the register tiles: workgroup per trajectory
+    });
 }
 
 bool dp_supported(int dtype, int n, int m, bool tv)

@@ -255,11 +255,10 @@ hipError_t dp_big_launch(const DpArgs &a, hipStream_t s)
     if (e != hipSuccess) return e;
     for (int64_t b0 = 0; b0 < a.batch && e == hipSuccess; b0 += chunk) {
         dim3 grid((unsigned)std::min<int64_t>(chunk, a.batch - b0)), block(BT);
-        if (a.dtype == 0)
-            hipLaunchKernelGGL((dp_big_kernel<double>), grid, block, 0, s, a, (double *)ws, elems, b0);
-        else
-            hipLaunchKernelGGL((dp_big_kernel<float>), grid, block, 0, s, a, (float *)ws, elems, b0);
-        e = hipGetLastError();
+        e = with_dtype(a.dtype, [&](auto t) {
+            hipLaunchKernelGGL((dp_big_kernel<decltype(t)>), grid, block, 0, s, a, (decltype(t) *)ws, elems, b0);
+            return hipGetLastError();
+        });
     }
     hipError_t ef = scratch_free(ws, s);
     return e != hipSuccess ? e : ef;

@@ -64,6 +64,7 @@ template <typename T, int NP, int MP, bool TV, bool SOA, bool LIN = false, bool 
           bool VALUE = false>
 __global__ __launch_bounds__(64) void dp_lane_kernel(const DpArgs a)
 {
+    static_assert((!AFF || LIN) && (!CROSS || AFF) && (!VALUE || CROSS), "each kind extends the one before it");
     const int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x;
     if (b >= a.batch) return;   // no barriers / cross-lane ops below
     const int n = a.n, m = a.m, N = a.N;
@@ -1088,39 +1089,25 @@ template <typename T, int MP>
 static hipError_t launch_hex(const DpArgs &a, hipStream_t s)
 {
     dim3 grid((unsigned)((a.batch * 16 + 63) / 64)), block(64);
-    if (a.layout == 1) hipLaunchKernelGGL((dp_hex_kernel<T, MP, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((dp_hex_kernel<T, MP, false>), grid, block, 0, s, a);
-    return hipGetLastError();
+    return with_bool(a.layout == 1, [&](auto soa) {
+        hipLaunchKernelGGL((dp_hex_kernel<T, MP, decltype(soa)::value>), grid, block, 0, s, a);
+        return hipGetLastError();
+    });
 }
 
 template <typename T, int NP, int MP>
-static hipError_t launch_lane(const DpArgs &a, hipStream_t s)
+static hipError_t launch_lane(const DpArgs &a, int kind, hipStream_t s)
 {
     dim3 grid((unsigned)((a.batch + 63) / 64)), block(64);
-    const bool tv = a.tv_AB || a.tv_QR, soa = a.layout == 1;
-    if (a.cross && !(a.lin && a.aff)) return hipErrorInvalidValue;   // the cross term extends the affine solve
-    if (a.value && !a.cross) return hipErrorInvalidValue;              // the constant extends the cross solve
-    if (a.value && tv && soa) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, true, true, true, true, true, true>), grid, block, 0, s, a);
-    else if (a.value && tv) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, true, false, true, true, true, true>), grid, block, 0, s, a);
-    else if (a.value && soa) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, false, true, true, true, true, true>), grid, block, 0, s, a);
-    else if (a.value) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, false, false, true, true, true, true>), grid, block, 0, s, a);
-    else if (a.cross && tv && soa) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, true, true, true, true, true>), grid, block, 0, s, a);
-    else if (a.cross && tv) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, true, false, true, true, true>), grid, block, 0, s, a);
-    else if (a.cross && soa) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, false, true, true, true, true>), grid, block, 0, s, a);
-    else if (a.cross) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, false, false, true, true, true>), grid, block, 0, s, a);
-    else if (a.aff && tv && soa) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, true, true, true, true>), grid, block, 0, s, a);
-    else if (a.aff && tv) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, true, false, true, true>), grid, block, 0, s, a);
-    else if (a.aff && soa) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, false, true, true, true>), grid, block, 0, s, a);
-    else if (a.aff) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, false, false, true, true>), grid, block, 0, s, a);
-    else if (a.lin && tv && soa) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, true, true, true>), grid, block, 0, s, a);
-    else if (a.lin && tv) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, true, false, true>), grid, block, 0, s, a);
-    else if (a.lin && soa) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, false, true, true>), grid, block, 0, s, a);
-    else if (a.lin) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, false, false, true>), grid, block, 0, s, a);
-    else if (tv && soa) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, true, true>), grid, block, 0, s, a);
-    else if (tv) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, true, false>), grid, block, 0, s, a);
-    else if (soa) hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, false, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, false, false>), grid, block, 0, s, a);
-    return hipGetLastError();
+    return with_kind(kind, [&](auto k) {
+        return with_bools(a.tv_AB || a.tv_QR, a.layout == 1, [&](auto tv, auto soa) {
+            constexpr int KIND = decltype(k)::value;
+            hipLaunchKernelGGL((dp_lane_kernel<T, NP, MP, decltype(tv)::value, decltype(soa)::value, KIND >= DP_LINEAR,
+                                               KIND >= DP_AFFINE, KIND >= DP_CROSS, KIND >= DP_VALUE>),
+                               grid, block, 0, s, a);
+            return hipGetLastError();
+        });
+    });
 }
 
 bool dp_lane_supported(int n, int m) { return n >= 1 && m >= 1 && n <= 4 && m <= 4; }
@@ -1141,12 +1128,14 @@ template <typename T, int MP>
 static hipError_t launch_quad(const DpArgs &a, hipStream_t s)
 {
     dim3 grid((unsigned)((a.batch * 4 + 63) / 64)), block(64);
-    if (a.lin && a.layout == 1) hipLaunchKernelGGL((dp_quad_kernel<T, MP, true, true>), grid, block, 0, s, a);
-    else if (a.lin) hipLaunchKernelGGL((dp_quad_kernel<T, MP, false, true>), grid, block, 0, s, a);
-    else if (a.layout == 1) hipLaunchKernelGGL((dp_quad_kernel<T, MP, true>), grid, block, 0, s, a);
-    else if (a.n == 4 && a.m == MP) hipLaunchKernelGGL((dp_quad_kernel<T, MP, false, false, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((dp_quad_kernel<T, MP, false>), grid, block, 0, s, a);
-    return hipGetLastError();
+    if (!a.lin && a.layout != 1 && a.n == 4 && a.m == MP) {
+        hipLaunchKernelGGL((dp_quad_kernel<T, MP, false, false, true>), grid, block, 0, s, a);
+        return hipGetLastError();
+    }
+    return with_bools(a.lin, a.layout == 1, [&](auto lin, auto soa) {
+        hipLaunchKernelGGL((dp_quad_kernel<T, MP, decltype(soa)::value, decltype(lin)::value>), grid, block, 0, s, a);
+        return hipGetLastError();
+    });
 }
 
 // hex kernel (16 lanes per trajectory; n ≤ 4, m ≤ 4, time-invariant, no linear terms): an
@@ -1160,43 +1149,21 @@ static bool use_hex(const DpArgs &a)
     return e && e[0] == 'h';
 }
 
-hipError_t dp_lane_launch(const DpArgs &a, hipStream_t s)
+hipError_t dp_lane_launch(const DpArgs &a, int kind, hipStream_t s)
 {
     const int np = a.n <= 2 ? 2 : 4, mp = a.m <= 1 ? 1 : (a.m <= 2 ? 2 : 4);
-    if (use_hex(a)) {
-        if (a.dtype == 0) {
-            if (mp == 1) return launch_hex<double, 1>(a, s);
-            if (mp == 2) return launch_hex<double, 2>(a, s);
-            return launch_hex<double, 4>(a, s);
-        }
-        if (mp == 1) return launch_hex<float, 1>(a, s);
-        if (mp == 2) return launch_hex<float, 2>(a, s);
-        return launch_hex<float, 4>(a, s);
-    }
-    if (use_quad(a)) {
-        if (a.dtype == 0) {
-            if (mp == 1) return launch_quad<double, 1>(a, s);
-            if (mp == 2) return launch_quad<double, 2>(a, s);
-            return launch_quad<double, 4>(a, s);
-        }
-        if (mp == 1) return launch_quad<float, 1>(a, s);
-        if (mp == 2) return launch_quad<float, 2>(a, s);
-        return launch_quad<float, 4>(a, s);
-    }
-    if (a.dtype == 0) {
-        if (np == 2 && mp == 1) return launch_lane<double, 2, 1>(a, s);
-        if (np == 2 && mp == 2) return launch_lane<double, 2, 2>(a, s);
-        if (np == 4 && mp == 1) return launch_lane<double, 4, 1>(a, s);
-        if (np == 4 && mp == 2) return launch_lane<double, 4, 2>(a, s);
-        if (np == 4 && mp == 4) return launch_lane<double, 4, 4>(a, s);
-    } else {
-        if (np == 2 && mp == 1) return launch_lane<float, 2, 1>(a, s);
-        if (np == 2 && mp == 2) return launch_lane<float, 2, 2>(a, s);
-        if (np == 4 && mp == 1) return launch_lane<float, 4, 1>(a, s);
-        if (np == 4 && mp == 2) return launch_lane<float, 4, 2>(a, s);
-        if (np == 4 && mp == 4) return launch_lane<float, 4, 4>(a, s);
-    }
-    return hipErrorNotSupported;
+    auto with_mp = [&](auto f) { return mp == 1 ? f(IntC<1>{}) : mp == 2 ? f(IntC<2>{}) : f(IntC<4>{}); };
+    return with_dtype(a.dtype, [&](auto t) {
+        using T = decltype(t);
+        if (use_hex(a)) return with_mp([&](auto MP) { return launch_hex<T, decltype(MP)::value>(a, s); });
+        if (use_quad(a)) return with_mp([&](auto MP) { return launch_quad<T, decltype(MP)::value>(a, s); });
+        if (np == 2 && mp == 1) return launch_lane<T, 2, 1>(a, kind, s);
+        if (np == 2 && mp == 2) return launch_lane<T, 2, 2>(a, kind, s);
+        if (np == 4 && mp == 1) return launch_lane<T, 4, 1>(a, kind, s);
+        if (np == 4 && mp == 2) return launch_lane<T, 4, 2>(a, kind, s);
+        if (np == 4 && mp == 4) return launch_lane<T, 4, 4>(a, kind, s);
+        return hipErrorNotSupported;
+    });
 }
 
 } // namespace lqrx

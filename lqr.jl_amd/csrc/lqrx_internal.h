@@ -1,6 +1,7 @@
 // lqrx_internal.h — kernel argument blocks shared by the launchers and the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include <vector>
 #include <stdint.h>
 
@@ -45,6 +46,30 @@ struct DpArgs {
     void *vs, *vdV;
 };
 
+// The DP solve kinds nest: each adds arguments to the one before it (lin; c; M; val).
+enum DpKind { DP_PLAIN, DP_LINEAR, DP_AFFINE, DP_CROSS, DP_VALUE };
+// the kind that a.lin / a.aff / a.cross / a.value spell, or −1 when the flags do not nest (dp_launch,
+// alone among the launchers, checks that and hands the kind down)
+inline int dp_kind(const DpArgs &a)
+{
+    const int f[4] = {a.lin != 0, a.aff != 0, a.cross != 0, a.value != 0};
+    return f[0] >= f[1] && f[1] >= f[2] && f[2] >= f[3] ? f[0] + f[1] + f[2] + f[3] : -1;
+}
+// Run-time value → compile-time constant, for the launchers: f is a generic lambda that returns
+// hipError_t; it reads its argument as decltype(x)::value (a bool, a kind) or decltype(x) (the type).
+template <typename F> hipError_t with_bool(bool b, F &&f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+template <typename F> hipError_t with_bools(bool b, bool c, F &&f)
+{
+    return with_bool(b, [&](auto x) { return with_bool(c, [&](auto y) { return f(x, y); }); });
+}
+template <typename F> hipError_t with_dtype(int dtype, F &&f) { return dtype == 0 ? f(double{}) : f(float{}); }
+template <int K> using IntC = std::integral_constant<int, K>;
+template <typename F> hipError_t with_kind(int kind, F &&f)
+{
+    return kind == DP_PLAIN ? f(IntC<DP_PLAIN>{}) : kind == DP_LINEAR ? f(IntC<DP_LINEAR>{})
+         : kind == DP_AFFINE ? f(IntC<DP_AFFINE>{}) : kind == DP_CROSS ? f(IntC<DP_CROSS>{})
+         : kind == DP_VALUE ? f(IntC<DP_VALUE>{}) : hipErrorInvalidValue;
+}
 hipError_t dp_launch(const DpArgs &a, hipStream_t s);
 // J = V_1(x0) = ½x0ᵀP_1x0 + p_1ᵀx0 + s_1 behind a value solve (lqrx_dp.hip): one thread per
 // trajectory on a's P, p, vs and x0 in a's layout, accumulated in double, written to J (batch)
@@ -54,7 +79,7 @@ hipError_t dp_value_cost_launch(const DpArgs &a, void *J, hipStream_t s);
 hipError_t batch_transpose(const void *in, void *out, int64_t rows, int64_t cols, int elem_bytes, hipStream_t s);
 bool dp_supported(int dtype, int n, int m, bool tv);
 // lane-per-trajectory kernel for n ≤ 4, m ≤ 4 (lqrx_dp_lane.hip)
-hipError_t dp_lane_launch(const DpArgs &a, hipStream_t s);
+hipError_t dp_lane_launch(const DpArgs &a, int kind, hipStream_t s);
 bool dp_lane_supported(int n, int m);
 // workgroup-per-trajectory kernel for shapes past the register tiles (lqrx_dp_big.hip):
 // n > 64 or m > 32, up to 512 each

@@ -1,9 +1,9 @@
 """Checkers for the costates and the adjoint pass of the DP solve (lqrx_dp_costates,
 lqrx_dp_solve_adjoint; include/lqrx.h).  Not a test file; pinned in tests/test_dp_adjoint.py.
 
-Problem, as in dp_cross_truth: stage cost ½xᵀQ_k x + uᵀM_k x + ½uᵀR_k u + q_kᵀx + r_kᵀu, terminal
+Problem, as in dp_truth: stage cost ½xᵀQ_k x + uᵀM_k x + ½uᵀR_k u + q_kᵀx + r_kᵀu, terminal
 ½xᵀQf x + qfᵀx, dynamics x_{k+1} = A_k x_k + B_k u_k + c_k, x_1 = x0.  Costates, with the sign
-λ_k = ∂V_k/∂x = P_k x_k + p_k (= −lam[k] of dense_cross_kkt):
+λ_k = ∂V_k/∂x = P_k x_k + p_k (= −lam[k] of dp_truth.dense_kkt):
 
     λ_N = Qf x_N + qf,      λ_k = Q_k x_k + M_kᵀu_k + q_k + A_kᵀλ_{k+1}
 
@@ -18,14 +18,13 @@ qf' = gX_N, r' = gU_k, c' = 0, x0' = 0 gives X', U', λ'; then
 
 Two checkers:
   (a) dense_adjoint_truth — torch CPU float64 autograd through the dense KKT solve of
-      dense_cross_kkt, Q, R, Qf entered as ½(Z + Zᵀ): X, U, λ and the eleven gradients of one problem;
+      dense_kkt, Q, R, Qf entered as ½(Z + Zᵀ): X, U, λ and the eleven gradients of one problem;
   (b) adjoint_abi — the numpy restatement of the recursion above for a batch of flat ABI arrays, in
       a chosen dtype (what the kernels are compared with).
 """
 import numpy as np
 
-from dp_affine_truth import _flat, _mats
-from dp_cross_truth import dp_solve_cross_abi
+from dp_truth import _flat, _mats, dp_solve_abi_np
 
 FIELDS = ("A", "B", "c", "Q", "R", "M", "Qf", "x0", "q", "r", "qf")
 
@@ -137,7 +136,7 @@ def costates_textbook(A, Q, M, Qf, q, qf, X, U, dtype=np.float64):
 
 
 def adjoint_abi(d: dict, N: int, gX, gU, dtype=np.float64) -> dict:
-    """Checker (b).  d: flat ABI arrays as for dp_solve_cross_abi (tv_AB / tv_QR optional); gX
+    """Checker (b).  d: flat ABI arrays as for dp_truth.dp_solve_abi_np (tv_AB / tv_QR optional); gX
     (bt, N, n), gU (bt, N−1, m).  Runs the forward solve, its costates, the adjoint solve, its
     costates and the formulas, every operation in `dtype`.  Returns logical arrays: X, U, lam, Xa,
     Ua, lama, info, and g = {field: gradient}: gA, gB, gc per knot (bt, N−1, …) with tv_AB, else summed
@@ -157,7 +156,7 @@ def adjoint_abi(d: dict, N: int, gX, gU, dtype=np.float64) -> dict:
     qf = np.asarray(d["qf"], dt).reshape(bt, n)
     B = _mats(d["B"], bt, kab, n, m, dt)
     r = np.asarray(d["r"], dt).reshape(bt, kqr, m)
-    fwd = dp_solve_cross_abi(d, N, dtype=dt)
+    fwd = dp_solve_abi_np(d, N, "cross", dtype=dt)
     X, U = fwd["X"].reshape(bt, N, n), fwd["U"].reshape(bt, N - 1, m)
     lam = costates_logical(A, B, Q, R, M, Qf, q, r, qf, _mats(fwd["K"], bt, N - 1, m, n, dt), X, U, dt)
     # the adjoint problem: per-knot cost terms (Q, R, M broadcast when time-invariant), q' r' qf' from gX gU
@@ -166,7 +165,7 @@ def adjoint_abi(d: dict, N: int, gX, gU, dtype=np.float64) -> dict:
     da.update(Q=_flat(bc(Q)), R=_flat(bc(R)), M=_flat(bc(M)), tv_QR=1,
               q=np.ascontiguousarray(gX[:, :N - 1]).ravel(), r=gU.ravel(),
               qf=np.ascontiguousarray(gX[:, N - 1]).ravel(), c=np.zeros(bt * kab * n, dt), x0=np.zeros(bt * n, dt))
-    adj = dp_solve_cross_abi(da, N, dtype=dt)
+    adj = dp_solve_abi_np(da, N, "cross", dtype=dt)
     Xa, Ua = adj["X"].reshape(bt, N, n), adj["U"].reshape(bt, N - 1, m)
     lama = costates_logical(A, B, Q, R, M, Qf, gX[:, :N - 1], gU, gX[:, N - 1],
                             _mats(adj["K"], bt, N - 1, m, n, dt), Xa, Ua, dt)

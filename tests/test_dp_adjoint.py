@@ -2,7 +2,7 @@
 
 The two checkers of tests/dp_adjoint_truth.py against each other — (b) the numpy restatement of
 the recursion the kernels implement, (a) torch float64 autograd through the dense KKT solve — at
-the shapes the GPU tests use, the sign of λ against dense_cross_kkt, the stationarity residual, a
+the shapes the GPU tests use, the sign of λ against dense_kkt, the stationarity residual, a
 central finite difference of the loss, and the argument checks of lqrx_dp_costates[_host] and
 lqrx_dp_solve_adjoint, which are decided before the device is touched.
 
@@ -17,7 +17,7 @@ import pytest
 
 from dp_adjoint_truth import (FIELDS, adjoint_abi, check_grads, dense_adjoint_truth, per_knot_problem,
                               sum_truth_like)
-from dp_cross_truth import cross_problem, dense_cross_kkt
+from dp_truth import cross_problem, dense_kkt
 
 TOL64 = 1e-10
 TOL32 = 1e-4
@@ -65,12 +65,12 @@ def test_recursion_matches_dense_autograd(lqrx, n, m, N, dtype, tol):
 
 @pytest.mark.parametrize("n,m,N", [(5, 2, 6), (2, 1, 4), (3, 2, 2)])
 def test_costate_sign_and_stationarity(lqrx, n, m, N):
-    """λ of (a) is −lam of dense_cross_kkt; R u + M x + r + Bᵀλ_{k+1} = 0 with (b)'s λ; x'_1 = 0."""
+    """λ of (a) is −lam of dense_kkt; R u + M x + r + Bᵀλ_{k+1} = 0 with (b)'s λ; x'_1 = 0."""
     d, gX, gU = problem(lqrx, n, m, N, 2, 77 + n, 1)
     ref = adjoint_abi(d, N, gX, gU)
     for b in range(2):
         p = per_knot_problem(d, N, b)
-        X, U, lam = dense_cross_kkt(p["A"], p["B"], p["c"], p["Q"], p["R"], p["M"], p["Qf"], p["x0"], N,
+        X, U, lam = dense_kkt(p["A"], p["B"], p["c"], p["Q"], p["R"], p["M"], p["Qf"], p["x0"], N,
                                     p["q"], p["r"], p["qf"])
         ta = dense_adjoint_truth(p, N, gX[b], gU[b])
         assert np.abs(ta["lam"] + lam).max() <= TOL64 * np.abs(lam).max()
@@ -89,13 +89,12 @@ def test_long_horizon_needs_the_closed_loop_sweep(lqrx):
     (observed 1.9e-5: ρ^(N−1) ≈ 2e14 times the rounding of X, U) — which is why the library and the
     checker add K_kᵀ·(stationarity)."""
     from dp_adjoint_truth import costates_textbook
-    from dp_affine_truth import _mats
-    from dp_cross_truth import dp_solve_cross_abi
+    from dp_truth import _mats, dp_solve_abi_np
 
     n, m, N, bt = 32, 16, 256, 2
     d, gX, gU = problem(lqrx, n, m, N, bt, 6100 + 13 * n + m, 1)
     ref = adjoint_abi(d, N, gX, gU)
-    full = dp_solve_cross_abi(d, N, all_P=True)
+    full = dp_solve_abi_np(d, N, "cross", all_P=True)
     P, p = _mats(full["P"], bt, N, n, n, np.float64), full["p"].reshape(bt, N, n)
     lamP = (P @ ref["X"][..., None])[..., 0] + p
     mx = lambda a: np.abs(a).reshape(bt, -1).max(axis=1)
@@ -111,7 +110,7 @@ def test_long_horizon_needs_the_closed_loop_sweep(lqrx):
 
 def test_finite_difference_of_the_loss(lqrx):
     """ℓ(θ + εδ) − ℓ(θ − εδ) over 2ε against Σ ⟨gradient, δ⟩ in three random directions, symmetric
-    in Q, R, Qf; ℓ from dense_cross_kkt (numpy).  ε = 1e-6: the truncation error is O(ε²) = 1e-12 and
+    in Q, R, Qf; ℓ from dense_kkt (numpy).  ε = 1e-6: the truncation error is O(ε²) = 1e-12 and
     the rounding error of ℓ about 1e-16·cond/ε ≈ 1e-10·cond relative, so 1e-6 of the sum of the terms'
     magnitudes holds with a wide margin for these well-conditioned problems."""
     n, m, N = 4, 2, 6
@@ -120,7 +119,7 @@ def test_finite_difference_of_the_loss(lqrx):
     g = adjoint_abi(d, N, gX, gU)["g"]
 
     def loss(q):
-        X, U, _ = dense_cross_kkt(q["A"], q["B"], q["c"], q["Q"], q["R"], q["M"], q["Qf"], q["x0"], N, q["q"],
+        X, U, _ = dense_kkt(q["A"], q["B"], q["c"], q["Q"], q["R"], q["M"], q["Qf"], q["x0"], N, q["q"],
                                   q["r"], q["qf"])
         return (X * gX[0]).sum() + (U * gU[0]).sum()
 

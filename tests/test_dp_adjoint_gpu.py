@@ -38,7 +38,7 @@ import pytest
 
 from dp_adjoint_truth import (FIELDS, adjoint_abi, check_grads, dense_adjoint_truth, per_knot_problem,
                               sum_truth_like)
-from dp_cross_truth import cross_problem
+from dp_truth import cross_problem
 
 pytestmark = pytest.mark.gpu
 

@@ -1,7 +1,7 @@
 """Affine dynamics x⁺ = A x + B u + c (lqrx_dp_solve_affine): the checker's identities, the
 ABI's argument codes and the wrapper's shape rules.  No device is needed.
 
-tests/dp_affine_truth.py restates the recursion in numpy; here it is pinned by
+tests/dp_truth.py restates the recursion in numpy; here it is pinned by
   1. the dense equality-constrained QP with rows x_{k+1} − A x_k − B u_k = c_k: X, U within
      1e-10 and P_k x_k + p_k = −(dynamics multiplier) within 1e-9 at every knot (the
      tolerances of tests/test_oracle.py::test_dp_oracle_linear_equals_dense_kkt);
@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as orc
-from dp_affine_truth import affine_problem, dense_affine_kkt, dp_solve_affine_abi
+from dp_truth import affine_problem, dense_kkt, dp_solve_abi_np
 
 
 @pytest.mark.parametrize("n,m,N", [(5, 2, 9), (3, 1, 6)])
@@ -23,7 +23,7 @@ def test_checker_equals_dense_qp(lqrx, n, m, N):
 
     bt = 3
     d = affine_problem(lqrx, n, m, N, bt, 61 + n, tv_QR=True, tv_AB=True)
-    out = dp_solve_affine_abi(d, N, all_P=True)
+    out = dp_solve_abi_np(d, N, "affine", all_P=True)
     assert (out["info"] == 0).all()
     X = out["X"].reshape(bt, N, n)
     U = out["U"].reshape(bt, N - 1, m)
@@ -35,7 +35,7 @@ def test_checker_equals_dense_qp(lqrx, n, m, N):
     q = d["q"].reshape(bt, N - 1, n); r = d["r"].reshape(bt, N - 1, m); qf = d["qf"].reshape(bt, n)
     c = d["c"].reshape(bt, N - 1, n)
     for t in range(bt):
-        Xd, Ud, lam = dense_affine_kkt(A[t], B[t], c[t], Q[t], R[t], Qf[t], x0[t], N, q[t], r[t], qf[t])
+        Xd, Ud, lam = dense_kkt(A[t], B[t], c[t], Q[t], R[t], None, Qf[t], x0[t], N, q[t], r[t], qf[t])
         sc = max(1.0, np.abs(Xd).max(), np.abs(Ud).max())
         eX, eU = np.abs(X[t] - Xd).max() / sc, np.abs(U[t] - Ud).max() / sc
         grad = np.einsum("kij,kj->ki", P[t], X[t]) + p[t]
@@ -51,7 +51,7 @@ def test_checker_zero_offset_equals_linear_oracle(lqrx, n, m, N):
     bt = 3
     d = affine_problem(lqrx, n, m, N, bt, 83 + n)
     d["c"] = np.zeros_like(d["c"])
-    a = dp_solve_affine_abi(d, N, all_P=True)
+    a = dp_solve_abi_np(d, N, "affine", all_P=True)
     b = orc.dp_solve_lin_abi(d, N, all_P=True)
     assert (a["info"] == 0).all() and (b["info"] == 0).all()
     for k in ("K", "P", "d", "p", "X", "U"):

@@ -1,6 +1,6 @@
 """GPU parity: DP with affine dynamics x⁺ = A x + B u + c (lqrx_dp_solve_affine).
 
-Checker: tests/dp_affine_truth.py (numpy float64; pinned to the dense QP and to the committed
+Checker: tests/dp_truth.py (numpy float64; pinned to the dense QP and to the committed
 oracle in tests/test_dp_affine.py).  Independently of it, the shift identity below compares
 against oracle.dp_solve_abi alone.  Tolerances are those of tests/test_dp_linear_gpu.py,
 measured the same way: fp64 1e-10, fp32 1e-4; K and P per knot, d, p, X, U on their
@@ -13,7 +13,7 @@ past the register tiles dp_big_kernel.
 import numpy as np
 import pytest
 
-from dp_affine_truth import affine_problem, dp_solve_affine_abi
+from dp_truth import PARITY, affine_problem, check, dp_solve_abi_np, logical, to_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -21,85 +21,12 @@ TOL64 = 1e-10
 TOL32 = 1e-4
 
 
-def relerr_per_knot(a, b):
-    a = a.reshape(a.shape[0], a.shape[1], -1)
-    b = b.reshape(b.shape[0], b.shape[1], -1)
-    num = np.abs(a - b).max(axis=2)
-    den = np.abs(b).max(axis=2)
-    den[den == 0] = 1.0
-    return float((num / den).max())
-
-
-def relerr_traj(a, b):
-    """max over trajectories of max|a−b| / max|b| over the whole trajectory."""
-    a = a.reshape(a.shape[0], -1)
-    b = b.reshape(b.shape[0], -1)
-    den = np.abs(b).max(axis=1)
-    den[den == 0] = 1.0
-    return float((np.abs(a - b).max(axis=1) / den).max())
-
-
-def to_batch(d, N, with_c=True):
-    from lqrx.dp import LQRBatch, from_abi
-
-    n, m, bt = d["n"], d["m"], d["batch"]
-    kab = N - 1 if d.get("tv_AB") else 1
-    kq = N - 1 if d.get("tv_QR") else 1
-    sh = lambda a, r, c, k: from_abi(a, (bt, k, r, c)) if k > 1 else from_abi(a, (bt, r, c))
-    vec = lambda a, w, k: a.reshape(bt, k, w) if k > 1 else a.reshape(bt, w)
-    return LQRBatch(sh(d["A"], n, n, kab), sh(d["B"], n, m, kab), sh(d["Q"], n, n, kq),
-                    sh(d["R"], m, m, kq), from_abi(d["Qf"], (bt, n, n)), d["x0"].reshape(bt, n), N,
-                    q=vec(d["q"], n, kq), r=vec(d["r"], m, kq), qf=d["qf"].reshape(bt, n),
-                    c=vec(d["c"], n, kab) if with_c else None)
-
-
-def logical(ref, n, m, N, bt, all_P):
-    """flat ABI result arrays → the logical arrays solve_batch returns"""
-    from lqrx.dp import from_abi
-
-    return dict(K=from_abi(ref["K"], (bt, N - 1, m, n)),
-                P=from_abi(ref["P"], (bt, N, n, n) if all_P else (bt, n, n)),
-                X=ref["X"].reshape(bt, N, n), U=ref["U"].reshape(bt, N - 1, m),
-                d=ref["d"].reshape(bt, N - 1, m),
-                p=ref["p"].reshape(bt, N, n) if all_P else ref["p"].reshape(bt, n), info=ref["info"])
-
-
-def check(got, ref, all_P, tol, what=""):
-    """got, ref: logical arrays.  Prints every figure, then asserts."""
-    e = dict(K=relerr_per_knot(got["K"], ref["K"]),
-             P=relerr_per_knot(got["P"], ref["P"]) if all_P else relerr_per_knot(got["P"][:, None], ref["P"][:, None]),
-             d=relerr_traj(got["d"], ref["d"]), p=relerr_traj(got["p"], ref["p"]))
-    for k in ("X", "U"):
-        e[k] = float(np.abs(got[k] - ref[k]).max() / max(1.0, np.abs(ref[k]).max()))
-    print(what, " ".join(f"{k} {v:.2e}" for k, v in e.items()))
-    assert (got["info"] == 0).all() and (ref["info"] == 0).all()
-    for k, v in e.items():
-        assert v <= tol, (k, v)
-
-
-PARITY = [
-    (1, 1, 6, 3, False, False, True),       # lane, degenerate
-    (4, 1, 40, 67, False, False, True),     # lane, partial second wave (quad-sized batch: the detour)
-    (3, 2, 40, 9, True, True, True),        # lane, time-varying
-    (2, 2, 30, 5, True, True, False),       # lane, time-varying, p_1 only
-    (6, 3, 30, 7, False, False, True),      # MFMA 1×1 padded
-    (17, 5, 12, 3, True, True, True),       # 2×1 padded, time-varying
-    (32, 16, 40, 4, False, False, True),    # 2×1 exact, time-invariant: dp_rollout_full
-    (32, 16, 256, 3, True, True, False),    # 2×1 exact, time-varying, full horizon, p_1 only
-    (24, 18, 10, 3, False, False, True),    # 2×2
-    (64, 32, 12, 2, False, False, True),    # fp64 n = 64: one-wave 4×2 (the wg4 detour)
-    (48, 16, 10, 2, True, True, True),      # 4×1 in the 4×2 grid, time-varying
-    (65, 4, 8, 2, False, False, True),      # big kernel
-    (70, 8, 9, 3, True, True, False),       # big kernel, time-varying
-]
-
-
 @pytest.mark.parametrize("n,m,N,bt,tvq,tvab,all_P", PARITY)
 def test_dp_affine_parity_f64(lqrx, gpu_ok, n, m, N, bt, tvq, tvab, all_P):
     d = affine_problem(lqrx, n, m, N, bt, 5100 + 11 * n + m, tvq, tvab)
     got = lqrx.solve_batch(to_batch(d, N), all_P=all_P)
     assert got["rc"] == 0
-    ref = logical(dp_solve_affine_abi(d, N, all_P=all_P), n, m, N, bt, all_P)
+    ref = logical(dp_solve_abi_np(d, N, "affine", all_P=all_P), n, m, N, bt, all_P)
     check(got, ref, all_P, TOL64, f"f64 {n},{m},{N},{bt}")
 
 
@@ -107,7 +34,7 @@ def test_dp_affine_parity_f64(lqrx, gpu_ok, n, m, N, bt, tvq, tvab, all_P):
 def test_dp_affine_parity_f32(lqrx, gpu_ok, n, m, N, bt, tv):
     d = affine_problem(lqrx, n, m, N, bt, 700 + n, tv, tv)
     got = lqrx.solve_batch(to_batch(d, N), dtype=1, all_P=True)
-    ref = logical(dp_solve_affine_abi(d, N, all_P=True), n, m, N, bt, True)
+    ref = logical(dp_solve_abi_np(d, N, "affine", all_P=True), n, m, N, bt, True)
     check(got, ref, True, TOL32, f"f32 {n},{m},{N},{bt}")
 
 
@@ -148,7 +75,7 @@ def test_dp_affine_zero_offset_equals_linear(lqrx, gpu_ok, n, m, N, bt):
     d = affine_problem(lqrx, n, m, N, bt, 19 + n)
     d["c"] = np.zeros_like(d["c"])
     a = lqrx.solve_batch(to_batch(d, N), all_P=True)
-    ref = lqrx.solve_batch(to_batch(d, N, with_c=False), all_P=True)
+    ref = lqrx.solve_batch(to_batch(d, N, fields=("q", "r", "qf")), all_P=True)
     check(a, ref, True, TOL64, f"c=0 {n},{m},{N},{bt}")
 
 
@@ -178,7 +105,7 @@ def test_dp_affine_device_stream(lqrx, gpu_ok):
         out = lqrx.dp_solve_device(t, N, p_mode=1, stream=s.cuda_stream)
     s.synchronize()
     got = logical({k: out[k].cpu().numpy() for k in ("K", "P", "X", "U", "d", "p", "info")}, n, m, N, bt, True)
-    ref = logical(dp_solve_affine_abi(d, N, all_P=True), n, m, N, bt, True)
+    ref = logical(dp_solve_abi_np(d, N, "affine", all_P=True), n, m, N, bt, True)
     check(got, ref, True, TOL64, "stream")
 
 
@@ -192,7 +119,7 @@ def test_dp_affine_info_matches_linear(lqrx, gpu_ok):
     R[2] = -R[2]
     d["R"] = to_abi(R).ravel()
     a = lqrx.solve_batch(to_batch(d, N))
-    ref = lqrx.solve_batch(to_batch(d, N, with_c=False))
+    ref = lqrx.solve_batch(to_batch(d, N, fields=("q", "r", "qf")))
     assert ref["info"][2] != 0 and (np.delete(ref["info"], 2) == 0).all()
     assert np.array_equal(a["info"], ref["info"])
 
@@ -213,5 +140,5 @@ def test_dp_affine_single_problem_api(lqrx, gpu_ok):
     lqrx.solve(sol, DPSolver.of(prob), prob)
     got = dict(K=sol.K[None], P=sol.P[None], X=sol.X[None], U=sol.U[None], d=sol.d[None], p=sol.p[None],
                info=np.array([sol.info]))
-    ref = logical(dp_solve_affine_abi(d, N, all_P=True), n, m, N, 1, True)
+    ref = logical(dp_solve_abi_np(d, N, "affine", all_P=True), n, m, N, 1, True)
     check(got, ref, True, TOL64, "single")

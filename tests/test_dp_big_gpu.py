@@ -9,8 +9,9 @@ trajectory's scale; fp32 within 1e-4 of the fp64 oracle.
 import numpy as np
 import pytest
 
-from test_dp_gpu import TOL32, TOL64, relerr_per_knot, run_pair
-from test_dp_linear_gpu import check, lin_problem, to_batch
+from dp_truth import relerr_per_knot, to_batch
+from test_dp_gpu import TOL32, TOL64, run_pair
+from test_dp_linear_gpu import check, lin_problem
 
 pytestmark = pytest.mark.gpu
 

@@ -1,11 +1,11 @@
 """Cost cross term uᵀMx (lqrx_dp_solve_cross): the checker's identities, the ABI's argument codes
 and the wrapper's shape rules.  No device is needed.
 
-tests/dp_cross_truth.py restates the recursion (G = BᵀPA + M_k) in numpy; here it is pinned by
+tests/dp_truth.py restates the recursion (G = BᵀPA + M_k) in numpy; here it is pinned by
   1. the dense equality-constrained QP with H[u_k, x_k] = M_k and its transpose: X, U within
      1e-10 and P_k x_k + p_k = −(dynamics multiplier) within 1e-9 at every knot (the tolerances of
      tests/test_dp_affine.py);
-  2. M = 0: K, P, d, p, X, U of dp_affine_truth.dp_solve_affine_abi within 1e-10;
+  2. M = 0: K, P, d, p, X, U of the affine kind, which ignores M, within 1e-10;
   3. the feedback-shift identity against the committed oracle alone: with u = ũ − F x the
      linear-terms problem (A, B, Q, R, q, r, qf) becomes the cross problem (A + BF, B, Q + FᵀRF, R,
      M = RF, q + Fᵀr, r, qf), c = 0, with the same P, p, d, X, and K = K̃ + F, U = Ũ − F X̃; 1e-10.
@@ -16,8 +16,8 @@ import numpy as np
 import pytest
 
 from oracle import oracle as orc
-from dp_affine_truth import affine_problem, dp_solve_affine_abi
-from dp_cross_truth import cross_problem, dense_cross_kkt, dp_solve_cross_abi
+from dp_truth import (affine_problem, cross_problem, dense_kkt, dp_solve_abi_np, feedback_shift,
+                      feedback_shift_reference)
 
 
 @pytest.mark.parametrize("n,m,N", [(5, 2, 9), (3, 1, 6)])
@@ -27,7 +27,7 @@ def test_checker_equals_dense_qp(lqrx, n, m, N):
 
     bt = 3
     d = cross_problem(lqrx, n, m, N, bt, 61 + n, tv_QR=True, tv_AB=True)
-    out = dp_solve_cross_abi(d, N, all_P=True)
+    out = dp_solve_abi_np(d, N, "cross", all_P=True)
     assert (out["info"] == 0).all()
     X = out["X"].reshape(bt, N, n)
     U = out["U"].reshape(bt, N - 1, m)
@@ -41,7 +41,7 @@ def test_checker_equals_dense_qp(lqrx, n, m, N):
     c = d["c"].reshape(bt, N - 1, n)
     assert np.abs(M).max() > 0.05                       # the term is there
     for t in range(bt):
-        Xd, Ud, lam = dense_cross_kkt(A[t], B[t], c[t], Q[t], R[t], M[t], Qf[t], x0[t], N, q[t], r[t], qf[t])
+        Xd, Ud, lam = dense_kkt(A[t], B[t], c[t], Q[t], R[t], M[t], Qf[t], x0[t], N, q[t], r[t], qf[t])
         sc = max(1.0, np.abs(Xd).max(), np.abs(Ud).max())
         eX, eU = np.abs(X[t] - Xd).max() / sc, np.abs(U[t] - Ud).max() / sc
         grad = np.einsum("kij,kj->ki", P[t], X[t]) + p[t]
@@ -57,45 +57,13 @@ def test_checker_zero_cross_equals_affine_checker(lqrx, n, m, N):
     bt = 3
     d = affine_problem(lqrx, n, m, N, bt, 83 + n)
     d["M"] = np.zeros(bt * m * n)
-    a = dp_solve_cross_abi(d, N, all_P=True)
-    b = dp_solve_affine_abi(d, N, all_P=True)
+    a = dp_solve_abi_np(d, N, "cross", all_P=True)
+    b = dp_solve_abi_np(d, N, "affine", all_P=True)
     assert (a["info"] == 0).all() and (b["info"] == 0).all()
     for k in ("K", "P", "d", "p", "X", "U"):
         e = np.abs(a[k] - b[k]).max() / max(1.0, np.abs(b[k]).max())
         print(f"n={n} m={m} N={N} {k}: {e:.2e}")
         assert e <= 1e-10, k
-
-
-def feedback_shift(lqrx, n, m, N, bt, seed):
-    """(d, F): d the linear-terms problem of affine_problem with c = 0 (flat ABI, time-invariant),
-    dx the cross problem it becomes under u = ũ − F x, F ~ 0.3/√n · N(0, 1) per trajectory."""
-    from lqrx.dp import from_abi, to_abi
-
-    d = affine_problem(lqrx, n, m, N, bt, seed)
-    d["c"] = np.zeros_like(d["c"])
-    F = 0.3 / np.sqrt(n) * np.random.default_rng(seed + 1).standard_normal((bt, m, n))
-    A = from_abi(d["A"], (bt, n, n)); B = from_abi(d["B"], (bt, n, m))
-    Q = from_abi(d["Q"], (bt, n, n)); R = from_abi(d["R"], (bt, m, m))
-    Ft = np.swapaxes(F, -1, -2)
-    dx = dict(d)
-    dx["A"] = to_abi(A + B @ F).ravel()
-    Qx = Q + Ft @ R @ F
-    dx["Q"] = to_abi((Qx + np.swapaxes(Qx, -1, -2)) / 2).ravel()
-    dx["M"] = to_abi(R @ F).ravel()
-    dx["q"] = (d["q"].reshape(bt, n) + np.einsum("bij,bj->bi", Ft, d["r"].reshape(bt, m))).ravel()
-    return d, dx, F
-
-
-def feedback_shift_reference(lin, F, n, m, N, bt):
-    """What the cross problem of feedback_shift must return, from the linear-terms solution `lin`
-    (flat ABI, all P): P, p, d, X unchanged, K = K̃ + F, U = Ũ − F X̃.  Logical arrays."""
-    from lqrx.dp import from_abi
-
-    K = from_abi(lin["K"], (bt, N - 1, m, n)) + F[:, None]
-    X = lin["X"].reshape(bt, N, n)
-    U = lin["U"].reshape(bt, N - 1, m) - np.einsum("bij,bkj->bki", F, X[:, :-1])
-    return dict(K=K, P=from_abi(lin["P"], (bt, N, n, n)), X=X, U=U, d=lin["d"].reshape(bt, N - 1, m),
-                p=lin["p"].reshape(bt, N, n), info=lin["info"])
 
 
 @pytest.mark.parametrize("n,m,N", [(6, 3, 20), (4, 1, 30)])
@@ -106,7 +74,7 @@ def test_checker_feedback_shift_identity(lqrx, n, m, N):
     bt = 3
     d, dx, F = feedback_shift(lqrx, n, m, N, bt, 300 + n)
     ref = feedback_shift_reference(orc.dp_solve_lin_abi(d, N, all_P=True), F, n, m, N, bt)
-    out = dp_solve_cross_abi(dx, N, all_P=True)
+    out = dp_solve_abi_np(dx, N, "cross", all_P=True)
     got = dict(K=from_abi(out["K"], (bt, N - 1, m, n)), P=from_abi(out["P"], (bt, N, n, n)),
                X=out["X"].reshape(bt, N, n), U=out["U"].reshape(bt, N - 1, m),
                d=out["d"].reshape(bt, N - 1, m), p=out["p"].reshape(bt, N, n))

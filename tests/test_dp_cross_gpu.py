@@ -1,6 +1,6 @@
 """GPU parity: DP with a cost cross term uᵀMx (lqrx_dp_solve_cross), G = BᵀPA + M_k.
 
-Checker: tests/dp_cross_truth.py (numpy float64; pinned to the dense QP, to the affine checker and
+Checker: tests/dp_truth.py (numpy float64; pinned to the dense QP, to the affine checker and
 to the committed oracle in tests/test_dp_cross.py).  Independently of it, the feedback-shift
 identity below compares against oracle.dp_solve_lin_abi alone.  Tolerances are those of
 tests/test_dp_linear_gpu.py and tests/test_dp_affine_gpu.py, measured the same way: fp64 1e-10,
@@ -15,29 +15,13 @@ dp_big_kernel.
 import numpy as np
 import pytest
 
-from dp_cross_truth import cross_problem, dp_solve_cross_abi
-from test_dp_affine_gpu import PARITY, check, logical
-from test_dp_cross import feedback_shift, feedback_shift_reference
+from dp_truth import (F32_SHAPES, PARITY, check, cross_problem, dp_solve_abi_np, feedback_shift,
+                      feedback_shift_reference, logical, to_batch)
 
 pytestmark = pytest.mark.gpu
 
 TOL64 = 1e-10
 TOL32 = 1e-4
-F32_SHAPES = [(6, 3, 30, 7, False), (32, 16, 40, 3, True), (64, 32, 12, 2, False)]
-
-
-def to_batch(d, N, with_M=True):
-    from lqrx.dp import LQRBatch, from_abi
-
-    n, m, bt = d["n"], d["m"], d["batch"]
-    kab = N - 1 if d.get("tv_AB") else 1
-    kq = N - 1 if d.get("tv_QR") else 1
-    sh = lambda a, r, c, k: from_abi(a, (bt, k, r, c)) if k > 1 else from_abi(a, (bt, r, c))
-    vec = lambda a, w, k: a.reshape(bt, k, w) if k > 1 else a.reshape(bt, w)
-    return LQRBatch(sh(d["A"], n, n, kab), sh(d["B"], n, m, kab), sh(d["Q"], n, n, kq),
-                    sh(d["R"], m, m, kq), from_abi(d["Qf"], (bt, n, n)), d["x0"].reshape(bt, n), N,
-                    q=vec(d["q"], n, kq), r=vec(d["r"], m, kq), qf=d["qf"].reshape(bt, n),
-                    c=vec(d["c"], n, kab), M=sh(d["M"], m, n, kq) if with_M else None)
 
 
 @pytest.mark.parametrize("n,m,N,bt,tvq,tvab,all_P", PARITY)
@@ -45,7 +29,7 @@ def test_dp_cross_parity_f64(lqrx, gpu_ok, n, m, N, bt, tvq, tvab, all_P):
     d = cross_problem(lqrx, n, m, N, bt, 5100 + 11 * n + m, tvq, tvab)
     got = lqrx.solve_batch(to_batch(d, N), all_P=all_P)
     assert got["rc"] == 0
-    ref = logical(dp_solve_cross_abi(d, N, all_P=all_P), n, m, N, bt, all_P)
+    ref = logical(dp_solve_abi_np(d, N, "cross", all_P=all_P), n, m, N, bt, all_P)
     check(got, ref, all_P, TOL64, f"f64 {n},{m},{N},{bt}")
 
 
@@ -53,7 +37,7 @@ def test_dp_cross_parity_f64(lqrx, gpu_ok, n, m, N, bt, tvq, tvab, all_P):
 def test_dp_cross_parity_f32(lqrx, gpu_ok, n, m, N, bt, tv):
     d = cross_problem(lqrx, n, m, N, bt, 700 + n, tv, tv)
     got = lqrx.solve_batch(to_batch(d, N), dtype=1, all_P=True)
-    ref = logical(dp_solve_cross_abi(d, N, all_P=True), n, m, N, bt, True)
+    ref = logical(dp_solve_abi_np(d, N, "cross", all_P=True), n, m, N, bt, True)
     check(got, ref, True, TOL32, f"f32 {n},{m},{N},{bt}")
 
 
@@ -75,7 +59,7 @@ def test_dp_cross_zero_cross_equals_affine(lqrx, gpu_ok, n, m, N, bt):
     d = cross_problem(lqrx, n, m, N, bt, 19 + n)
     d["M"] = np.zeros_like(d["M"])
     a = lqrx.solve_batch(to_batch(d, N), all_P=True)
-    ref = lqrx.solve_batch(to_batch(d, N, with_M=False), all_P=True)
+    ref = lqrx.solve_batch(to_batch(d, N, fields=("q", "r", "qf", "c")), all_P=True)
     check(a, ref, True, TOL64, f"M=0 {n},{m},{N},{bt}")
 
 
@@ -106,7 +90,7 @@ def test_dp_cross_device_stream(lqrx, gpu_ok):
         out = lqrx.dp_solve_device(t, N, p_mode=1, stream=s.cuda_stream)
     s.synchronize()
     got = logical({k: out[k].cpu().numpy() for k in ("K", "P", "X", "U", "d", "p", "info")}, n, m, N, bt, True)
-    ref = logical(dp_solve_cross_abi(d, N, all_P=True), n, m, N, bt, True)
+    ref = logical(dp_solve_abi_np(d, N, "cross", all_P=True), n, m, N, bt, True)
     check(got, ref, True, TOL64, "stream")
 
 
@@ -121,7 +105,7 @@ def test_dp_cross_info_matches_checker(lqrx, gpu_ok):
     R[2] = -R[2]
     d["R"] = to_abi(R).ravel()
     a = lqrx.solve_batch(to_batch(d, N))
-    ref = dp_solve_cross_abi(d, N)
+    ref = dp_solve_abi_np(d, N, "cross")
     print("info", a["info"], ref["info"])
     assert ref["info"][2] != 0 and (np.delete(ref["info"], 2) == 0).all()
     assert np.array_equal(a["info"], ref["info"])
@@ -144,5 +128,5 @@ def test_dp_cross_single_problem_api(lqrx, gpu_ok):
     lqrx.solve(sol, DPSolver.of(prob), prob)
     got = dict(K=sol.K[None], P=sol.P[None], X=sol.X[None], U=sol.U[None], d=sol.d[None], p=sol.p[None],
                info=np.array([sol.info]))
-    ref = logical(dp_solve_cross_abi(d, N, all_P=True), n, m, N, 1, True)
+    ref = logical(dp_solve_abi_np(d, N, "cross", all_P=True), n, m, N, 1, True)
     check(got, ref, True, TOL64, "single")

@@ -12,8 +12,7 @@ value kind (s then holds every s_k and is staged like p).
 import numpy as np
 import pytest
 
-from dp_cross_truth import cross_problem
-from test_dp_cross_gpu import to_batch
+from dp_truth import cross_problem, to_batch
 
 pytestmark = pytest.mark.gpu
 

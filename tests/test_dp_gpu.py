@@ -7,20 +7,12 @@ Tolerance (north star): max|K − K_ref| / max|K_ref| ≤ 1e-10 per knot in fp64
 import numpy as np
 import pytest
 
+from dp_truth import relerr_per_knot
+
 pytestmark = pytest.mark.gpu
 
 TOL64 = 1e-10
 TOL32 = 1e-4
-
-
-def relerr_per_knot(a, b):
-    """max over knots of max|a−b| / max|b| (leading axes: batch, knot)."""
-    a = a.reshape(a.shape[0], a.shape[1], -1)
-    b = b.reshape(b.shape[0], b.shape[1], -1)
-    num = np.abs(a - b).max(axis=2)
-    den = np.abs(b).max(axis=2)
-    den[den == 0] = 1.0
-    return float((num / den).max())
 
 
 def run_pair(lqrx, oracle, n, m, N, batch, seed, dtype=0, all_P=True):

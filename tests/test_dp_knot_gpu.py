@@ -20,6 +20,8 @@ import sys
 import numpy as np
 import pytest
 
+from dp_truth import relerr_per_knot
+
 pytestmark = pytest.mark.gpu
 
 TOL = {0: 1e-10, 1: 1e-4}
@@ -27,14 +29,6 @@ N, BT = 6, 3
 # (n, m, dtype): fp64 NT=1 | NT=2 (the headline grid) | padded NT=2 | NT=3 ; fp32 NT=4
 GRIDS = [(16, 16, 0), (32, 16, 0), (17, 3, 0), (48, 16, 0), (64, 32, 1)]
 _cache = {}
-
-
-def relerr_per_knot(a, b):
-    a = a.reshape(a.shape[0], a.shape[1], -1).astype(np.float64)
-    b = b.reshape(b.shape[0], b.shape[1], -1)
-    den = np.abs(b).max(axis=2)
-    den[den == 0] = 1.0
-    return float((np.abs(a - b).max(axis=2) / den).max())
 
 
 def _run(lqrx, oracle, n, m, dtype):

@@ -10,7 +10,8 @@ fp32 1e-4 against the fp64 oracle.
 import numpy as np
 import pytest
 
-from test_dp_gpu import TOL32, TOL64, relerr_per_knot, run_pair
+from dp_truth import relerr_per_knot
+from test_dp_gpu import TOL32, TOL64, run_pair
 
 pytestmark = pytest.mark.gpu
 

@@ -13,19 +13,12 @@ Kernels: n ≤ 4 dp_lane_kernel<…, LIN>, n ≥ 5 dp_riccati_kernel<…, VAR_TV
 import numpy as np
 import pytest
 
+from dp_truth import relerr_per_knot, relerr_traj, to_batch
+
 pytestmark = pytest.mark.gpu
 
 TOL64 = 1e-10
 TOL32 = 1e-4
-
-
-def relerr_per_knot(a, b):
-    a = a.reshape(a.shape[0], a.shape[1], -1)
-    b = b.reshape(b.shape[0], b.shape[1], -1)
-    num = np.abs(a - b).max(axis=2)
-    den = np.abs(b).max(axis=2)
-    den[den == 0] = 1.0
-    return float((num / den).max())
 
 
 def lin_problem(lqrx, n, m, N, bt, seed, tv_QR=False, tv_AB=False):
@@ -52,28 +45,6 @@ def lin_problem(lqrx, n, m, N, bt, seed, tv_QR=False, tv_AB=False):
         d["B"] = to_abi(B.reshape(-1, n, m)).ravel()
         d["tv_AB"] = 1
     return d
-
-
-def to_batch(d, N):
-    from lqrx.dp import LQRBatch, from_abi
-
-    n, m, bt = d["n"], d["m"], d["batch"]
-    kab = N - 1 if d.get("tv_AB") else 1
-    kq = N - 1 if d.get("tv_QR") else 1
-    sh = lambda a, r, c, k: from_abi(a, (bt, k, r, c)) if k > 1 else from_abi(a, (bt, r, c))
-    vec = lambda a, w, k: a.reshape(bt, k, w) if k > 1 else a.reshape(bt, w)
-    return LQRBatch(sh(d["A"], n, n, kab), sh(d["B"], n, m, kab), sh(d["Q"], n, n, kq),
-                    sh(d["R"], m, m, kq), from_abi(d["Qf"], (bt, n, n)), d["x0"].reshape(bt, n), N,
-                    q=vec(d["q"], n, kq), r=vec(d["r"], m, kq), qf=d["qf"].reshape(bt, n))
-
-
-def relerr_traj(a, b):
-    """max over trajectories of max|a−b| / max|b| over the whole trajectory."""
-    a = a.reshape(a.shape[0], -1)
-    b = b.reshape(b.shape[0], -1)
-    den = np.abs(b).max(axis=1)
-    den[den == 0] = 1.0
-    return float((np.abs(a - b).max(axis=1) / den).max())
 
 
 def check(got, ref, n, m, N, bt, all_P, tol):

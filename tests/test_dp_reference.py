@@ -1,9 +1,9 @@
 """oracle.dp_reference — the DP recursion in one precision (float32, float64 or longdouble) with
 its own Cholesky — pinned against the checkers the suite already trusts.  No device is needed.
 
-On one benign problem (n = 6, m = 3, N = 12, three trajectories of dp_affine_truth.affine_problem),
+On one benign problem (n = 6, m = 3, N = 12, three trajectories of dp_truth.affine_problem),
 time-invariant and with every field per knot:
-  1. float64, with q, r, qf, c: K, P, d, p, X, U of dp_affine_truth.dp_solve_affine_abi within 1e-12;
+  1. float64, with q, r, qf, c: K, P, d, p, X, U of dp_truth.dp_solve_abi_np (affine) within 1e-12;
   2. float64, plain: K, P, X, U of oracle.dp_solve_abi (the C oracle) within 1e-12;
   3. longdouble against float64 within 1e-11 — the precisions run the same code;
 and dp_extended is the longdouble run, an indefinite E is reported at its knot, float32 stays
@@ -12,7 +12,7 @@ float32.  Errors are max|a − b| / max|b| over the whole array.
 import numpy as np
 import pytest
 
-from dp_affine_truth import affine_problem, dp_solve_affine_abi
+from dp_truth import affine_problem, dp_solve_abi_np
 
 n, m, N, BT = 6, 3, 12, 3
 
@@ -46,7 +46,7 @@ def test_reference_f64_equals_checkers(lqrx, oracle, tv):
     d = affine_problem(lqrx, n, m, N, BT, 501, tv_QR=tv, tv_AB=tv)
     L = _logical(d)
     got = _run(oracle, L, np.float64)
-    ref = dp_solve_affine_abi(d, N, all_P=True)
+    ref = dp_solve_abi_np(d, N, "affine", all_P=True)
     assert (got["info"] == 0).all() and (ref["info"] == 0).all()
     want = dict(K=from_abi(ref["K"], (BT, N - 1, m, n)), P=from_abi(ref["P"], (BT, N, n, n)),
                 d=ref["d"].reshape(BT, N - 1, m), p=ref["p"].reshape(BT, N, n),

@@ -1,9 +1,9 @@
 """Value-function constant (lqrx_dp_solve_value): the checker's identities, the ABI's argument codes
 and the wrapper's rules.  No device is needed.
 
-tests/dp_value_truth.py extends dp_cross_truth's recursion with s_k, dV = Σ h_kᵀd_k and
+tests/dp_truth.py extends the cross recursion with s_k, dV = Σ h_kᵀd_k and
 J = V_1(x0); here it is pinned by
-  1. the dense equality-constrained QP of dp_cross_truth.dense_cross_kkt: J equals the cost of the
+  1. the dense equality-constrained QP of dp_truth.dense_kkt: J equals the cost of the
      QP's optimum, evaluated term by term by cost_of(), within 1e-10 of max(1, S + |J|);
   2. c = 0 ⇒ s_1 = −½dV;
   3. s_N = 0, and the all-P s_1 equals the P_1-only s.
@@ -13,8 +13,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from dp_cross_truth import cross_problem, dense_cross_kkt
-from dp_value_truth import cost_of, dp_solve_value_abi
+from dp_truth import cost_of, cross_problem, dense_kkt, dp_solve_abi_np
 
 
 def _per_knot(a, bt, k, N, *shape):
@@ -33,7 +32,7 @@ def test_checker_cost_equals_dense_qp(lqrx, n, m, N, tv):
 
     bt = 3
     d = cross_problem(lqrx, n, m, N, bt, 900 + n, tv_QR=tv, tv_AB=tv)
-    out = dp_solve_value_abi(d, N)
+    out = dp_solve_abi_np(d, N, "value")
     assert (out["info"] == 0).all()
     k = N - 1 if tv else 1
     A = _per_knot(d["A"], bt, k, N, n, n); B = _per_knot(d["B"], bt, k, N, n, m)
@@ -44,7 +43,7 @@ def test_checker_cost_equals_dense_qp(lqrx, n, m, N, tv):
     assert np.abs(c).max() > 0.01 and np.abs(q).max() > 0.01      # the constant is not −½dV here
     Xd = np.zeros((bt, N, n)); Ud = np.zeros((bt, N - 1, m))
     for t in range(bt):
-        Xd[t], Ud[t], _ = dense_cross_kkt(A[t], B[t], c[t], Q[t], R[t], M[t], Qf[t], x0[t], N, q[t], r[t], qf[t])
+        Xd[t], Ud[t], _ = dense_kkt(A[t], B[t], c[t], Q[t], R[t], M[t], Qf[t], x0[t], N, q[t], r[t], qf[t])
     Jqp = cost_of(d, Xd, Ud)
     Jro = cost_of(d, out["X"], out["U"])
     sc = np.maximum(1, out["S"] + np.abs(Jqp))
@@ -59,7 +58,7 @@ def test_checker_zero_offset_constant_is_minus_half_dV(lqrx):
     n, m, N, bt = 6, 3, 20, 3
     d = cross_problem(lqrx, n, m, N, bt, 77)
     d["c"] = np.zeros_like(d["c"])
-    out = dp_solve_value_abi(d, N)
+    out = dp_solve_abi_np(d, N, "value")
     e = np.abs(out["s"] + 0.5 * out["dV"]) / np.maximum(1, out["S"])
     print("s_1 + dV/2:", e, "dV", out["dV"])
     assert (out["dV"] > 0).all() and e.max() <= 1e-14
@@ -69,8 +68,8 @@ def test_checker_p_modes_agree(lqrx):
     """Identity 3: s_N = 0; the all-P s_1 is the P_1-only s."""
     n, m, N, bt = 5, 2, 9, 3
     d = cross_problem(lqrx, n, m, N, bt, 78, tv_QR=True, tv_AB=True)
-    a = dp_solve_value_abi(d, N, all_P=True)
-    b = dp_solve_value_abi(d, N)
+    a = dp_solve_abi_np(d, N, "value", all_P=True)
+    b = dp_solve_abi_np(d, N, "value")
     sa = a["s"].reshape(bt, N)
     assert (sa[:, N - 1] == 0).all()
     assert np.array_equal(sa[:, 0], b["s"]) and np.array_equal(a["dV"], b["dV"]) and np.array_equal(a["J"], b["J"])

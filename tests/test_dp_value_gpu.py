@@ -1,9 +1,9 @@
 """GPU parity: the value function's constant (lqrx_dp_solve_value) — s_k, dV = Σ h_kᵀd_k and
 J = V_1(x0) on top of the cross solve.
 
-Checker: tests/dp_value_truth.py (numpy float64; pinned to the dense QP in tests/test_dp_value.py).
+Checker: tests/dp_truth.py (numpy float64; pinned to the dense QP in tests/test_dp_value.py).
 Independently of it, J is compared with the cost of the GPU's own X, U, evaluated term by term.
-Error measures (dp_value_truth.value_errors): s and dV relative to max(1, S), J relative to
+Error measures (dp_truth.value_errors): s and dV relative to max(1, S), J relative to
 max(1, S + |J|), S = Σ_k (|c_kᵀ(p + ½Pc_k)| + ½|h_kᵀd_k|) per trajectory.  Tolerances are the
 project's: fp64 1e-10, fp32 1e-4.
 The fp32 bound: the checker run in float32 against float64 on the CPU at the three fp32 shapes
@@ -18,10 +18,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from dp_cross_truth import cross_problem
-from dp_value_truth import cost_of, dp_solve_value_abi, value_errors
-from test_dp_affine_gpu import PARITY, check, logical
-from test_dp_cross_gpu import F32_SHAPES, to_batch
+from dp_truth import (F32_SHAPES, PARITY, check, cost_of, cross_problem, dp_solve_abi_np, logical, to_batch,
+                      value_errors)
 
 pytestmark = pytest.mark.gpu
 
@@ -45,7 +43,7 @@ def test_dp_value_parity_f64(lqrx, gpu_ok, n, m, N, bt, tvq, tvab, all_P):
     d = cross_problem(lqrx, n, m, N, bt, 5100 + 11 * n + m, tvq, tvab)
     got = lqrx.solve_batch(to_batch(d, N), all_P=all_P, value=True)
     assert got["rc"] == 0
-    ref = dp_solve_value_abi(d, N, all_P=all_P)
+    ref = dp_solve_abi_np(d, N, "value", all_P=all_P)
     assert got["s"].shape == ((bt, N) if all_P else (bt,))
     check(got, logical(ref, n, m, N, bt, all_P), all_P, TOL64, f"f64 {n},{m},{N},{bt}")
     check_value(got, ref, TOL64, f"f64 {n},{m},{N},{bt}")
@@ -55,7 +53,7 @@ def test_dp_value_parity_f64(lqrx, gpu_ok, n, m, N, bt, tvq, tvab, all_P):
 def test_dp_value_parity_f32(lqrx, gpu_ok, n, m, N, bt, tv):
     d = cross_problem(lqrx, n, m, N, bt, 700 + n, tv, tv)
     got = lqrx.solve_batch(to_batch(d, N), dtype=1, all_P=True, value=True)
-    ref = dp_solve_value_abi(d, N, all_P=True)
+    ref = dp_solve_abi_np(d, N, "value", all_P=True)
     assert got["s"].dtype == np.float32 and got["J"].dtype == np.float32
     check_value(got, ref, TOL32, f"f32 {n},{m},{N},{bt}")
 
@@ -68,7 +66,7 @@ def test_dp_value_cost_of_own_rollout(lqrx, gpu_ok, n, m, N, bt):
     got = lqrx.solve_batch(to_batch(d, N), value=True)
     assert (got["info"] == 0).all()
     J = cost_of(d, got["X"], got["U"])
-    S = dp_solve_value_abi(d, N)["S"]
+    S = dp_solve_abi_np(d, N, "value")["S"]
     e = np.abs(got["J"] - J) / np.maximum(1, S + np.abs(J))
     print(f"{n},{m},{N},{bt}: J {got['J']} cost {J} err {e.max():.2e}")
     assert e.max() <= TOL64
@@ -92,7 +90,7 @@ def test_dp_value_zero_offset(lqrx, gpu_ok):
     d = cross_problem(lqrx, n, m, N, bt, 515)
     d["c"] = np.zeros_like(d["c"])
     got = lqrx.solve_batch(to_batch(d, N), value=True)
-    S = dp_solve_value_abi(d, N)["S"]
+    S = dp_solve_abi_np(d, N, "value")["S"]
     e = np.abs(got["s"] + 0.5 * got["dV"]) / np.maximum(1, S)
     print("s_1 + dV/2:", e)
     assert (got["dV"] > 0).all() and e.max() <= TOL64
@@ -177,7 +175,7 @@ def test_dp_value_device_stream(lqrx, gpu_ok):
     with torch.cuda.stream(s):
         out = lqrx.dp_solve_device(t, N, p_mode=1, stream=s.cuda_stream, value=True)
     s.synchronize()
-    ref = dp_solve_value_abi(d, N, all_P=True)
+    ref = dp_solve_abi_np(d, N, "value", all_P=True)
     got = logical({k: out[k].cpu().numpy() for k in OUT}, n, m, N, bt, True)
     check(got, logical(ref, n, m, N, bt, True), True, TOL64, "stream")
     check_value({k: out[k].cpu().numpy() for k in ("s", "dV", "J")}, ref, TOL64, "stream")
@@ -194,7 +192,7 @@ def test_dp_value_info_leaves_other_trajectories_alone(lqrx, gpu_ok):
     R[2] = -R[2]
     d["R"] = to_abi(R).ravel()
     a = lqrx.solve_batch(to_batch(d, N), all_P=True, value=True)
-    ref = dp_solve_value_abi(d, N, all_P=True)
+    ref = dp_solve_abi_np(d, N, "value", all_P=True)
     print("info", a["info"], ref["info"])
     assert ref["info"][2] != 0 and (np.delete(ref["info"], 2) == 0).all()
     assert np.array_equal(a["info"], ref["info"])
@@ -215,7 +213,7 @@ def test_dp_value_single_problem_api(lqrx, gpu_ok):
                       q=d["q"].copy(), r=d["r"].copy(), qf=d["qf"].copy(), c=d["c"].copy())
     sol = LQRSolution.of(prob, all_P=True, value=True)
     lqrx.solve(sol, DPSolver.of(prob), prob)
-    ref = dp_solve_value_abi(d, N, all_P=True)
+    ref = dp_solve_abi_np(d, N, "value", all_P=True)
     got = dict(K=sol.K[None], P=sol.P[None], X=sol.X[None], U=sol.U[None], d=sol.d[None], p=sol.p[None],
                info=np.array([sol.info]))
     check(got, logical(ref, n, m, N, 1, True), True, TOL64, "single")

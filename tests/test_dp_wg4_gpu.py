@@ -16,20 +16,13 @@ import sys
 import numpy as np
 import pytest
 
+from dp_truth import relerr_per_knot, to_batch
 from test_dp_lane_gpu import _tv_batch
-from test_dp_linear_gpu import check, lin_problem, to_batch
+from test_dp_linear_gpu import check, lin_problem
 
 pytestmark = pytest.mark.gpu
 
 TOL64 = 1e-10
-
-
-def relerr_per_knot(a, b):
-    a = a.reshape(a.shape[0], a.shape[1], -1)
-    b = b.reshape(b.shape[0], b.shape[1], -1)
-    den = np.abs(b).max(axis=2)
-    den[den == 0] = 1.0
-    return float((np.abs(a - b).max(axis=2) / den).max())
 
 
 @pytest.mark.parametrize("m,tv_ab,tv_qr,N,bt,all_P", [
@@ -103,7 +96,8 @@ def test_wg4_time_varying_info_middle_knot(lqrx, oracle, gpu_ok):
 _CODE = """
 import sys, numpy as np, lqrx
 sys.path.insert(0, sys.argv[2])
-from test_dp_linear_gpu import lin_problem, to_batch
+from dp_truth import to_batch
+from test_dp_linear_gpu import lin_problem
 d = lin_problem(lqrx, 64, 32, 22, 2, 9, tv_QR=True, tv_AB=True)
 g = lqrx.solve_batch(to_batch(d, 22), all_P=True)
 np.save(sys.argv[1], np.concatenate([g[k].ravel() for k in ("K", "P", "X", "U", "d", "p")]))

@@ -18,6 +18,8 @@ import os
 import numpy as np
 import pytest
 
+from dp_truth import relerr_per_knot
+
 pytestmark = pytest.mark.gpu
 
 TOL64 = 1e-10
@@ -29,14 +31,6 @@ def sample_index(batch, k):
     idx = np.unique(np.linspace(0, batch - 1, k).round().astype(np.int64))
     assert idx[0] == 0 and idx[-1] == batch - 1
     return idx
-
-
-def relerr_per_knot(a, b):
-    a = a.reshape(a.shape[0], a.shape[1], -1)
-    b = b.reshape(b.shape[0], b.shape[1], -1)
-    den = np.abs(b).max(axis=2)
-    den[den == 0] = 1.0
-    return float((np.abs(a - b).max(axis=2) / den).max())
 
 
 def traj_err(a, b):

@@ -9,7 +9,7 @@ filled with the pattern too).  Asserted: guarded.check() passes (every guard of 
 output untouched, every output element written and finite); the guarded outputs are the plain
 outputs bit for bit (a read past an input that reached the result would differ, the neighbour now
 being a NaN); info == 0; and the plain outputs meet the project's checkers at the project's
-tolerances — dp_cross_truth.dp_solve_cross_abi for K, P, X, U, d, p, dp_value_truth for s, dV, J,
+tolerances — dp_truth.dp_solve_abi_np for K, P, X, U, d, p and for s, dV, J,
 TOL64 = 1e-10 / TOL32 = 1e-4 on the measures of tests/test_dp_cross_gpu.py and test_dp_value_gpu.py.
 No tolerance is introduced here.
 
@@ -31,10 +31,9 @@ import functools
 import numpy as np
 import pytest
 
-from dp_cross_truth import cross_problem, dp_solve_cross_abi
-from dp_value_truth import dp_solve_value_abi, value_errors
+from dp_truth import (cross_problem, dp_solve_abi_np, logical, relerr_per_knot, relerr_traj, to_batch,
+                      value_errors)
 from guarded import check as guard_check, guard_all, pattern_filled
-from test_dp_affine_gpu import logical, relerr_per_knot, relerr_traj
 
 pytestmark = pytest.mark.gpu
 
@@ -110,7 +109,7 @@ def truth(shape, tv, kind, pm):
         if k not in KINDS[kind]:
             d[k] = np.zeros_like(d[k])
     N = shape[2]
-    return dp_solve_value_abi(d, N, all_P=bool(pm)) if kind == "value" else dp_solve_cross_abi(d, N, all_P=bool(pm))
+    return dp_solve_abi_np(d, N, "value", all_P=bool(pm)) if kind == "value" else dp_solve_abi_np(d, N, "cross", all_P=bool(pm))
 
 
 def out_sizes(shape, kind, pm):
@@ -160,7 +159,7 @@ def same_bits(a, b):
 
 def parity(o, ref, shape, kind, pm, layout, tol, what):
     """The measures of test_dp_affine_gpu.check (K, P per knot; d, p on the trajectory's scale; X, U
-    on max(1, max|ref|)) and of dp_value_truth.value_errors; prints every figure, then asserts."""
+    on max(1, max|ref|)) and of dp_truth.value_errors; prints every figure, then asserts."""
     from lqrx.dp import from_soa
 
     n, m, N, bt = shape
@@ -306,7 +305,6 @@ def test_dp_host_entries_write_exactly_their_outputs(lqrx, gpu_ok, kind, layout,
     the same bytes to the same entry on plain np.zeros buffers)."""
     from lqrx import _lib
     from lqrx.dp import from_soa, to_soa
-    from test_dp_cross_gpu import to_batch
 
     n, m, N, bt = shape
     d = problem(shape, 0)

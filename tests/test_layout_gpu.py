@@ -9,7 +9,8 @@ here on the SoA result directly.
 import numpy as np
 import pytest
 
-from test_dp_gpu import TOL64, relerr_per_knot
+from dp_truth import relerr_per_knot
+from test_dp_gpu import TOL64
 
 pytestmark = pytest.mark.gpu
 

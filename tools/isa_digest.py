@@ -7,7 +7,15 @@ the source text — is replaced by a fixed token, and the SHA-256 of the listing
 trees whose digests agree ship the same device code: the evidence for a refactor of these files
 (profiles/r08/knobs/).  Reads nothing but the tree; needs no GPU.
 
-  tools/isa_digest.py [--root TREE] [--jobs N] [--keep DIR] [unit.hip ...]
+With --per-kernel: one line `sha256  unit  symbol` per function, sorted by symbol, for a refactor
+that reorders the functions of a unit (profiles/r09/kinds/).  The hash covers the function's body,
+label to `.Lfunc_end`, and its `.amdhsa_kernel … .end_amdhsa_kernel` block, after stripping `;`
+comments and trailing blanks and rewriting what only says where the function stands in the unit:
+`BB<i>_<j>` → `BB_<j>`, `.Lfunc_end<i>` → `.Lfunc_end`, and the long-branch labels
+`.Lpost_getpc<i>`, which the assembler printer numbers across the unit, renumbered from 0 in each
+function.
+
+  tools/isa_digest.py [--per-kernel] [--root TREE] [--jobs N] [--keep DIR] [unit.hip ...]
 """
 import argparse
 import concurrent.futures
@@ -27,21 +35,57 @@ def make_var(makefile, name):
     return m.group(1).strip()
 
 
-def digest(csrc, hipcc, flags, unit, keep):
+def normalise(asm):
+    return re.sub(rb"__hip_cuid_[0-9a-f]+", b"__hip_cuid_X", asm)
+
+
+def per_kernel(asm):
+    """{symbol: sha256} of every function of a listing (bytes), position-independent."""
+    text = re.sub(r"[ \t]*;[^\n]*", "", normalise(asm).decode(errors="replace"))
+    text = re.sub(r"[ \t]+$", "", text, flags=re.M)
+    text = re.sub(r"BB\d+_(\d+)", r"BB_\1", text)
+    text = re.sub(r"\.Lfunc_end\d+", ".Lfunc_end", text)
+    funcs = set(re.findall(r"^\s*\.type\s+([^\s,]+),\s*@function", text, re.M))
+    parts, sym, end = {f: [] for f in funcs}, None, None
+    for line in text.split("\n"):
+        if sym is None:
+            m = re.match(r"\s*\.amdhsa_kernel (\S+)$", line)
+            if line.endswith(":") and line[:-1] in funcs:
+                sym, end = line[:-1], ".Lfunc_end:"
+            elif m and m.group(1) in funcs:
+                sym, end = m.group(1), ".end_amdhsa_kernel"
+        if sym is not None:
+            parts[sym].append(line)
+            if line.strip() == end:
+                sym = None
+    if sym is not None or not all(parts.values()):
+        sys.exit("isa_digest: a function without a body or an end in the listing")
+    out = {}
+    for f, lines in parts.items():
+        body, order = "\n".join(lines), {}
+        for lab in re.findall(r"\.Lpost_getpc\d+", body):     # numbered across the unit: renumber per function
+            order.setdefault(lab, len(order))
+        body = re.sub(r"\.Lpost_getpc\d+", lambda m: f".Lpost_getpc_{order[m.group(0)]}", body)
+        out[f] = hashlib.sha256(body.encode()).hexdigest()
+    return out
+
+
+def digest(csrc, hipcc, flags, unit, keep, split):
     r = subprocess.run([hipcc, *flags, "--cuda-device-only", "-S", unit, "-o", "-"],
                        cwd=csrc, capture_output=True)
     if r.returncode:
         return unit, None, r.stderr.decode(errors="replace")
-    asm = re.sub(rb"__hip_cuid_[0-9a-f]+", b"__hip_cuid_X", r.stdout)
+    asm = normalise(r.stdout)
     if keep:
         (keep / (unit + ".s")).write_bytes(asm)
-    return unit, hashlib.sha256(asm).hexdigest(), ""
+    return unit, per_kernel(asm) if split else hashlib.sha256(asm).hexdigest(), ""
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--root", type=pathlib.Path, default=pathlib.Path(__file__).resolve().parent.parent,
                     help="tree to digest (default: the one this script is in)")
+    ap.add_argument("--per-kernel", action="store_true", help="one line per function instead of one per unit")
     ap.add_argument("--jobs", type=int, default=10)
     ap.add_argument("--keep", type=pathlib.Path, help="also write the normalised listings here")
     ap.add_argument("units", nargs="*", help="unit file names (default: every csrc/*.hip)")
@@ -55,14 +99,18 @@ def main():
     if a.keep:
         a.keep.mkdir(parents=True, exist_ok=True)
         a.keep = a.keep.resolve()
-    bad = 0
+    bad, lines = 0, []
     with concurrent.futures.ThreadPoolExecutor(max(1, a.jobs)) as ex:
-        for unit, sha, err in ex.map(lambda u: digest(csrc, hipcc, flags, u, a.keep), units):
+        for unit, sha, err in ex.map(lambda u: digest(csrc, hipcc, flags, u, a.keep, a.per_kernel), units):
             if sha is None:
                 bad += 1
                 print(f"isa_digest: {unit} failed to compile\n{err}", file=sys.stderr)
+            elif a.per_kernel:
+                lines += [(sym, f"{h}  {unit}  {sym}") for sym, h in sha.items()]
             else:
                 print(f"{sha}  {unit}", flush=True)
+    for _, line in sorted(lines):
+        print(line)
     return 1 if bad else 0
 
 

@@ -49,8 +49,8 @@ extern "C" {
                                    lqrx_dp_solve_affine[_host], lqrx_dp_solve_cross[_host] and
                                    lqrx_dp_solve_value[_host] are additive to ABI 5 (no existing
                                    signature or struct changed, the number stays 5): detect
-                                   them by symbol (dlsym); so are lqrx_dp_costates[_host] and
-                                   lqrx_dp_solve_adjoint */
+                                   them by symbol (dlsym); so are lqrx_dp_costates[_host],
+                                   lqrx_dp_solve_adjoint and lqrx_dp_rollout[_host] */
 
 #define LQRX_F64 0
 #define LQRX_F32 1
@@ -371,6 +371,66 @@ int lqrx_dp_solve_adjoint(const lqrx_dp_desc *desc, const void *A, const void *B
                           const void *R, const void *M, const void *Qf, const void *X,
                           const void *U, const void *lam, const lqrx_dp_grad *grad,
                           int32_t *info, void *stream);
+
+/* ------------------------------------------------------------------------------------
+ * Closed-loop rollout of a solved policy over many scenarios: the policy (K_k, d_k) of one solve,
+ * which does not depend on x0, run from S initial states per problem, with a step length α per
+ * scenario (the line-search direction u = −Kx − αd), a process disturbance w and actuator limits.
+ * Per problem b and scenario j (trajectory t = b·S + j):
+ *   x_1 = x0_t
+ *   u_k = min(max(−K_k x_k − α_t d_k, u_lo_b), u_hi_b)
+ *   x_{k+1} = A_k x_k + B_k u_k + c_k + w_{t,k}                                  k = 1 … N−1
+ *   J_t = Σ_k (½x_kᵀQ_k x_k + u_kᵀM_k x_k + ½u_kᵀR_k u_k + q_kᵀx_k + r_kᵀu_k) + ½x_NᵀQf x_N + qfᵀx_N
+ *   A, B        the dynamics (knot_stride_AB)
+ *   c           n·batch, or n·(N−1)·batch with knot_stride_AB = 1; may be NULL (zero)
+ *   K           the solve's gains, m·n·(N−1)·batch
+ *   d           the solve's feedforward, m·(N−1)·batch; may be NULL (zero)
+ *   cost        Q, R, M, q, r follow knot_stride_QR; Qf, qf per problem.  Needed only for J: cost may
+ *               be NULL when sc->J is NULL; with J, Q, R and Qf are required, M, q, r, qf may be NULL
+ *   sc          the scenarios, laid out scenario-major so that every scenario is a solve-shaped
+ *               trajectory and S = 1 is exactly the solve's X / U layout:
+ *                 x0_t at [t·n]            α_t at [t]          w_{t,k} at [(t·(N−1) + k−1)·n]
+ *                 x_k  at [(t·N + k−1)·n]  u_k at [(t·(N−1) + k−1)·m]            J_t at [t]
+ *               alpha NULL means α = 1, w NULL means no disturbance, u_lo / u_hi NULL mean no bound
+ *               on that side (±inf entries are allowed in either); u_lo ≤ u_hi is a precondition and
+ *               is not checked.  X, U, J are each optional, at least one is required.
+ * The element type is desc.dtype; desc.p_mode is ignored.  Every (n, m ≤ 512, dtype, knot stride)
+ * that lqrx_dp_solve_cross accepts is accepted, for any S ≥ 1; desc.layout = 1 returns
+ * LQRX_ERR_UNSUPPORTED.  Error codes follow the argument position and are decided before the device
+ * is touched: desc −1, A −2, B −3, K −5, cost −7 (J asked for and cost, or its Q, R or Qf, NULL),
+ * sc −8 (sc NULL, S < 1, x0 NULL, or X, U and J all NULL; lqrx_last_error names the member);
+ * batch = 0 returns 0.
+ * Guaranteed:
+ *   - a scenario's X, U and J are the same bits whatever S is, whatever its position j is, and
+ *     whichever of X, U, J are asked for (without J no cost arithmetic is done at all);
+ *   - alpha = NULL gives the bits of an all-ones alpha, u_lo = u_hi = NULL those of −inf / +inf;
+ *   - results are the same bits from run to run (no atomics);
+ *   - the device entry takes no scratch from the library pool: it is one kernel launch on `stream`,
+ *     and can be enqueued or captured like lqrx_kkt_solve_ws.
+ * Additive to ABI 5: detect by symbol.
+ * ------------------------------------------------------------------------------------ */
+typedef struct lqrx_dp_cost {          /* the stage / terminal cost, to form J */
+    const void *Q, *R, *Qf;            /* required when J is asked for          */
+    const void *M, *q, *r, *qf;        /* each may be NULL (zero)               */
+} lqrx_dp_cost;
+
+typedef struct lqrx_dp_scenarios {
+    int64_t S;                         /* scenarios per problem, >= 1           */
+    const void *x0;                    /* n·S·batch, required                   */
+    const void *alpha;                 /* S·batch, or NULL (= 1)                */
+    const void *w;                     /* n·(N−1)·S·batch, or NULL (= 0)        */
+    const void *u_lo, *u_hi;           /* m·batch each, or NULL (no bound); ±inf allowed */
+    void *X, *U, *J;                   /* out, each optional, at least one      */
+} lqrx_dp_scenarios;
+
+int lqrx_dp_rollout(const lqrx_dp_desc *desc, const void *A, const void *B, const void *c,
+                    const void *K, const void *d, const lqrx_dp_cost *cost,
+                    const lqrx_dp_scenarios *sc, void *stream);
+
+/* host pointers everywhere (in cost and sc too): H2D, rollout, D2H of the outputs asked for, synchronous */
+int lqrx_dp_rollout_host(const lqrx_dp_desc *desc, const void *A, const void *B, const void *c,
+                         const void *K, const void *d, const lqrx_dp_cost *cost,
+                         const lqrx_dp_scenarios *sc);
 
 /* ------------------------------------------------------------------------------------
  * KKT path: one inner solve of CholeskySolver._solve!(solver)

@@ -125,6 +125,53 @@ static void dp_null_sweep(double *buf, int32_t *info)
         }
 }
 
+// ---- lqrx_dp_rollout[_host]: every required pointer NULL in turn, bad S, no output, J without its
+// cost — minus the argument's position (A 2, B 3, K 5, cost 7, sc 8), decided with no device ----
+static int rollout_call(bool host, const lqrx_dp_desc *d, const void *A, const void *B, const void *c, const void *K,
+                        const void *dd, const lqrx_dp_cost *cost, const lqrx_dp_scenarios *sc)
+{
+    return host ? lqrx_dp_rollout_host(d, A, B, c, K, dd, cost, sc) : lqrx_dp_rollout(d, A, B, c, K, dd, cost, sc, nullptr);
+}
+
+static void rollout_sweep(double *buf)
+{
+    lqrx_dp_desc d{};
+    d.n = 8; d.m = 4; d.N = 10; d.dtype = LQRX_F64; d.batch = 4;
+    const lqrx_dp_cost cost{buf, buf, buf, buf, buf, buf, buf};
+    const lqrx_dp_scenarios sc{5, buf, buf, buf, buf, buf, buf, buf, buf};
+    for (int host = 0; host < 2; ++host) {
+        CHECK(rollout_call(host, nullptr, buf, buf, buf, buf, buf, &cost, &sc) == -1);
+        CHECK(rollout_call(host, &d, nullptr, buf, buf, buf, buf, &cost, &sc) == -2 && std::strstr(lqrx_last_error(), "A"));
+        CHECK(rollout_call(host, &d, buf, nullptr, buf, buf, buf, &cost, &sc) == -3 && std::strstr(lqrx_last_error(), "B"));
+        CHECK(rollout_call(host, &d, buf, buf, buf, nullptr, buf, &cost, &sc) == -5 && std::strstr(lqrx_last_error(), "K"));
+        CHECK(rollout_call(host, &d, buf, buf, buf, buf, buf, nullptr, &sc) == -7 && std::strstr(lqrx_last_error(), "cost"));
+        CHECK(rollout_call(host, &d, buf, buf, buf, buf, buf, &cost, nullptr) == -8 && std::strstr(lqrx_last_error(), "sc"));
+        lqrx_dp_cost cb = cost; cb.Q = nullptr;
+        CHECK(rollout_call(host, &d, buf, buf, buf, buf, buf, &cb, &sc) == -7 && std::strstr(lqrx_last_error(), "cost->Q"));
+        cb = cost; cb.R = nullptr;
+        CHECK(rollout_call(host, &d, buf, buf, buf, buf, buf, &cb, &sc) == -7 && std::strstr(lqrx_last_error(), "cost->R"));
+        cb = cost; cb.Qf = nullptr;
+        CHECK(rollout_call(host, &d, buf, buf, buf, buf, buf, &cb, &sc) == -7 && std::strstr(lqrx_last_error(), "cost->Qf"));
+        lqrx_dp_scenarios sb = sc; sb.S = 0;
+        CHECK(rollout_call(host, &d, buf, buf, buf, buf, buf, &cost, &sb) == -8 && std::strstr(lqrx_last_error(), "sc->S"));
+        sb = sc; sb.S = -3;
+        CHECK(rollout_call(host, &d, buf, buf, buf, buf, buf, &cost, &sb) == -8 && std::strstr(lqrx_last_error(), "sc->S"));
+        sb = sc; sb.x0 = nullptr;
+        CHECK(rollout_call(host, &d, buf, buf, buf, buf, buf, &cost, &sb) == -8 && std::strstr(lqrx_last_error(), "sc->x0"));
+        sb = sc; sb.X = sb.U = sb.J = nullptr;
+        CHECK(rollout_call(host, &d, buf, buf, buf, buf, buf, nullptr, &sb) == -8 && std::strstr(lqrx_last_error(), "sc->X"));
+        lqrx_dp_desc bad = d;
+        bad.layout = 1;
+        CHECK(rollout_call(host, &bad, buf, buf, buf, buf, buf, &cost, &sc) == LQRX_ERR_UNSUPPORTED);
+        bad = d; bad.n = 0;
+        CHECK(rollout_call(host, &bad, nullptr, buf, buf, buf, buf, &cost, &sc) == -1);
+        bad = d; bad.p_mode = 7;                         // p_mode is ignored: the next check answers
+        CHECK(rollout_call(host, &bad, nullptr, buf, buf, buf, buf, &cost, &sc) == -2);
+        bad = d; bad.batch = 0;                          // empty batch: a no-op whatever the pointers
+        CHECK(rollout_call(host, &bad, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == 0);
+    }
+}
+
 int main()
 {
     CHECK(lqrx_abi_version() == LQRX_ABI_VERSION);
@@ -169,6 +216,7 @@ int main()
         CHECK(lqrx_dp_solve_linear(&d, dummy, dummy, dummy, dummy, dummy, dummy, &ln, dummy, nullptr, dummy, dummy, info, nullptr) == -10);
     }
     dp_null_sweep(dummy, info);
+    rollout_sweep(dummy);
     b = d; b.batch = 0;                                          // empty batch: nothing to do
     CHECK(lqrx_dp_solve(&b, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == 0);
     if (!have_gpu) {                                             // valid call, no device: clean failure

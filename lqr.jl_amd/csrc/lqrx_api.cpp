@@ -678,6 +678,109 @@ int lqrx_dp_costates_host(const lqrx_dp_desc *d, const void *A, const void *B, c
     return e ? e : st;
 }
 
+} // extern "C"
+
+namespace {
+// The checks of lqrx_dp_rollout[_host] behind desc, in argument order (A 2, B 3, K 5, cost 7, sc 8;
+// c 4 and d 6 may be NULL).  sc comes before cost only as far as cost needs it: whether J is asked for.
+int check_rollout_args(const void *A, const void *B, const void *K, const lqrx_dp_cost *cost,
+                       const lqrx_dp_scenarios *sc)
+{
+    if (!A) return set_err(-2, "pointer 2 (A) is NULL");
+    if (!B) return set_err(-3, "pointer 3 (B) is NULL");
+    if (!K) return set_err(-5, "pointer 5 (K) is NULL");
+    if (!sc) return set_err(-8, "pointer 8 (sc) is NULL");
+    if (sc->J) {
+        if (!cost) return set_err(-7, "pointer 7 (cost) is NULL and sc->J is asked for");
+        if (!cost->Q) return set_err(-7, "cost->Q is NULL and sc->J is asked for");
+        if (!cost->R) return set_err(-7, "cost->R is NULL and sc->J is asked for");
+        if (!cost->Qf) return set_err(-7, "cost->Qf is NULL and sc->J is asked for");
+    }
+    if (sc->S < 1) return set_err(-8, "sc->S must be >= 1 (got %lld)", (long long)sc->S);
+    if (!sc->x0) return set_err(-8, "sc->x0 is NULL");
+    if (!sc->X && !sc->U && !sc->J) return set_err(-8, "sc->X, sc->U and sc->J are all NULL: nothing to compute");
+    return 0;
+}
+
+lqrx::DpScenArgs scen_args(const lqrx_dp_desc *d, const void *A, const void *B, const void *c, const void *K,
+                           const void *dd, const lqrx_dp_cost *cost, const lqrx_dp_scenarios *sc)
+{
+    lqrx::DpScenArgs a{};
+    a.A = A; a.B = B; a.c = c; a.K = K; a.d = dd;
+    if (sc->J) {   // the cost is read only for J
+        a.Q = cost->Q; a.R = cost->R; a.Qf = cost->Qf; a.M = cost->M; a.q = cost->q; a.r = cost->r; a.qf = cost->qf;
+    }
+    a.x0 = sc->x0; a.alpha = sc->alpha; a.w = sc->w; a.u_lo = sc->u_lo; a.u_hi = sc->u_hi;
+    a.X = sc->X; a.U = sc->U; a.J = sc->J;
+    a.n = d->n; a.m = d->m; a.N = d->N; a.dtype = d->dtype;
+    a.tv_AB = (int)d->knot_stride_AB; a.tv_QR = (int)d->knot_stride_QR;
+    a.batch = d->batch; a.S = sc->S;
+    return a;
+}
+} // namespace
+
+extern "C" {
+
+// closed-loop rollout of the policy (K, d) over sc->S scenarios per problem (see lqrx.h): one kernel, no scratch
+int lqrx_dp_rollout(const lqrx_dp_desc *d, const void *A, const void *B, const void *c, const void *K,
+                    const void *dd, const lqrx_dp_cost *cost, const lqrx_dp_scenarios *sc, void *stream)
+{
+    int st = validate_dp_adjoint(d, "lqrx_dp_rollout");
+    if (st) return st;
+    if (d->batch == 0) return 0;
+    if ((st = check_rollout_args(A, B, K, cost, sc))) return st;
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = lqrx::dp_scen_launch(scen_args(d, A, B, c, K, dd, cost, sc), s);
+    if (e == hipErrorNotSupported) return set_err(LQRX_ERR_UNSUPPORTED, "no rollout kernel for n=%d m=%d", d->n, d->m);
+    if (e != hipSuccess) return hip_err(e, "rollout kernel launch");
+    if (stream == nullptr && (e = hipStreamSynchronize(nullptr)) != hipSuccess) return hip_err(e, "rollout kernel");
+    return 0;
+}
+
+int lqrx_dp_rollout_host(const lqrx_dp_desc *d, const void *A, const void *B, const void *c, const void *K,
+                         const void *dd, const lqrx_dp_cost *cost, const lqrx_dp_scenarios *sc)
+{
+    int st = validate_dp_adjoint(d, "lqrx_dp_rollout_host");
+    if (st) return st;
+    if (d->batch == 0) return 0;
+    if ((st = check_rollout_args(A, B, K, cost, sc))) return st;
+    const size_t es = dsize(d->dtype), bt = (size_t)d->batch, n = d->n, m = d->m, N = d->N, S = (size_t)sc->S;
+    const size_t kAB = d->knot_stride_AB ? N - 1 : 1, kQR = d->knot_stride_QR ? N - 1 : 1;
+    const lqrx_dp_cost none{};
+    const lqrx_dp_cost &ct = sc->J ? *cost : none;   // without J the cost is not read: nothing to stage
+    enum { iA, iB, ic, iK, id, iQ, iR, iQf, iM, iq, ir, iqf, ix0, ial, iw, ilo, ihi, iX, iU, iJ, kBufs };
+    static_assert(kBufs <= DpTable::kMaxRows + 1, "HostStage holds kMaxRows + 1 twins");
+    HostBuf hb[kBufs];
+    hb[iA] = host_in(A, n * n * kAB * es * bt);
+    hb[iB] = host_in(B, n * m * kAB * es * bt);
+    hb[ic] = host_in(c, n * kAB * es * bt);
+    hb[iK] = host_in(K, m * n * (N - 1) * es * bt);
+    hb[id] = host_in(dd, m * (N - 1) * es * bt);
+    hb[iQ] = host_in(ct.Q, n * n * kQR * es * bt);
+    hb[iR] = host_in(ct.R, m * m * kQR * es * bt);
+    hb[iQf] = host_in(ct.Qf, n * n * es * bt);
+    hb[iM] = host_in(ct.M, m * n * kQR * es * bt);
+    hb[iq] = host_in(ct.q, n * kQR * es * bt);
+    hb[ir] = host_in(ct.r, m * kQR * es * bt);
+    hb[iqf] = host_in(ct.qf, n * es * bt);
+    hb[ix0] = host_in(sc->x0, n * S * es * bt);
+    hb[ial] = host_in(sc->alpha, S * es * bt);
+    hb[iw] = host_in(sc->w, n * (N - 1) * S * es * bt);
+    hb[ilo] = host_in(sc->u_lo, m * es * bt);
+    hb[ihi] = host_in(sc->u_hi, m * es * bt);
+    hb[iX] = HostBuf{sc->X, n * N * S * es * bt, H_OUT};   // only the outputs asked for have a twin
+    hb[iU] = HostBuf{sc->U, m * (N - 1) * S * es * bt, H_OUT};
+    hb[iJ] = HostBuf{sc->J, S * es * bt, H_OUT};
+    HostStage dev;
+    if ((st = dev.upload(hb, kBufs))) return st;
+    const lqrx_dp_cost dcost{dev[iQ], dev[iR], dev[iQf], dev[iM], dev[iq], dev[ir], dev[iqf]};
+    const lqrx_dp_scenarios dsc{sc->S, dev[ix0], dev[ial], dev[iw], dev[ilo], dev[ihi], dev[iX], dev[iU], dev[iJ]};
+    st = lqrx_dp_rollout(d, dev[iA], dev[iB], dev[ic], dev[iK], dev[id], sc->J ? &dcost : nullptr, &dsc, nullptr);
+    if (st < 0) return st;
+    const int e = dev.download(hb, kBufs);
+    return e ? e : st;
+}
+
 // Gradients of a loss ℓ(X, U) through the solve: one more cross solve with ∂ℓ/∂X, ∂ℓ/∂U as the
 // linear cost terms (x0' = 0, c' = 0), its costates, and the rank-2 assembly (see lqrx.h)
 int lqrx_dp_solve_adjoint(const lqrx_dp_desc *d, const void *A, const void *B, const void *Q, const void *R,

@@ -116,6 +116,23 @@ struct DpGradArgs {
 };
 hipError_t dp_grad_launch(const DpGradArgs &a, hipStream_t s);
 
+// ---- closed-loop rollout of a policy over S scenarios per problem (lqrx_dp_scen.hip), layout 0 only ----
+// Trajectory t = b·S + j: x_1 = x0_t, u_k = clamp(−K_k x_k − α_t d_k, u_lo_b, u_hi_b),
+// x_{k+1} = A_k x_k + B_k u_k + c_k + w_{t,k}; J_t the cost of the trajectory.  A, B, c follow tv_AB,
+// Q, R, M, q, r follow tv_QR; K and d are the solve's, per knot.  X, U, J are laid out per trajectory
+// like a solve's outputs with batch·S trajectories.  Takes no scratch.
+struct DpScenArgs {
+    const void *A, *B, *c, *K, *d;              // c, d may be null (zero)
+    const void *Q, *R, *Qf, *M, *q, *r, *qf;    // read only when J is set; M, q, r, qf may be null (zero)
+    const void *x0, *alpha, *w, *u_lo, *u_hi;   // alpha (null: 1), w (null: 0), u_lo / u_hi (null: no bound)
+    void *X, *U, *J;                            // each may be null (not formed)
+    int n, m, N;
+    int dtype; // 0 f64, 1 f32
+    int tv_AB, tv_QR;
+    int64_t batch, S;
+};
+hipError_t dp_scen_launch(const DpScenArgs &a, hipStream_t s);
+
 struct KktArgs {
     const double *Y, *y, *H, *g; // device, packed per trajectory
     double *dz, *lam;

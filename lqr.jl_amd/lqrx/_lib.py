@@ -47,6 +47,18 @@ class DpGrad(C.Structure):
                                           "gx0", "gq", "gr", "gqf")]
 
 
+class DpCost(C.Structure):
+    """Mirror of ``lqrx_dp_cost`` (the cost of lqrx_dp_rollout's J: Q, R, Qf required; M, q, r, qf optional)."""
+
+    _fields_ = [(k, C.c_void_p) for k in ("Q", "R", "Qf", "M", "q", "r", "qf")]
+
+
+class DpScenarios(C.Structure):
+    """Mirror of ``lqrx_dp_scenarios`` (S, x0 required; alpha, w, u_lo, u_hi optional in; X, U, J optional out)."""
+
+    _fields_ = [("S", C.c_int64)] + [(k, C.c_void_p) for k in ("x0", "alpha", "w", "u_lo", "u_hi", "X", "U", "J")]
+
+
 class KktDesc(C.Structure):
     """Mirror of ``lqrx_kkt_desc``."""
 
@@ -126,6 +138,8 @@ _SIGS = {
     "lqrx_dp_compute_ctg_host": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 8),
     "lqrx_dp_costates": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 13 + [_VP]),
     "lqrx_dp_costates_host": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 13),
+    "lqrx_dp_rollout": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 5 + [C.POINTER(DpCost), C.POINTER(DpScenarios), _VP]),
+    "lqrx_dp_rollout_host": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 5 + [C.POINTER(DpCost), C.POINTER(DpScenarios)]),
     "lqrx_dp_solve_adjoint": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 9 + [C.POINTER(DpGrad)]
                               + [_VP, _VP]),
     "lqrx_kkt_solve_host_devices": (C.c_int, [C.POINTER(KktDesc)] + [_VP] * 7 + [_VP, C.c_int32]),

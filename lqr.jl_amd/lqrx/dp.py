@@ -30,7 +30,7 @@ from . import _lib
 
 __all__ = ["LQRProblem", "LQRSolution", "DPSolver", "solve", "solve_batch", "LQRBatch",
            "random_batch", "to_abi", "from_abi", "dp_solve_device", "compute_gain", "compute_ctg",
-           "compute_ctg_batch"]
+           "compute_ctg_batch", "rollout_batch", "dp_rollout_device"]
 
 
 def to_abi(a: np.ndarray) -> np.ndarray:
@@ -463,3 +463,103 @@ def dp_solve_device(t: dict, N: int, p_mode: int = 0, stream: int | None = None,
                                         p(out["U"]), p(out["lam"]), st))
     out["rc"] = rc
     return out
+
+
+_ROLLOUT_OUT = ("X", "U", "J")
+
+
+def rollout_batch(b: LQRBatch, K, d, x0, alpha=None, w=None, u_lo=None, u_hi=None, dtype: int = _lib.F64,
+                  outputs=("X", "U", "J")) -> dict:
+    """Closed-loop rollout of the policy (K, d) of a solve over S scenarios per problem, through
+    lqrx_dp_rollout_host: x_1 = x0, u_k = clip(−K_k x_k − α d_k, u_lo, u_hi), x_{k+1} = A_k x_k + B_k u_k
+    + c_k + w_k, and the cost J of every trajectory.
+
+    b gives A, B (and c; and Q, R, Qf, M, q, r, qf when J is asked for); its own x0 is not used.
+    K (batch, N−1, m, n) and d (batch, N−1, m), or None for zero, are the solve's.  x0 (batch, S, n);
+    alpha (batch, S) or None (1); w (batch, S, N−1, n) or None (0); u_lo, u_hi (batch, m) or None (no
+    bound; ±inf entries allowed).  Returns those of X (batch, S, N, n), U (batch, S, N−1, m),
+    J (batch, S) that `outputs` names, and the ABI return code rc."""
+    n, m, N = b.size()
+    bt = b.batch
+    tvAB, tvQR = b.time_varying()
+    npdt = np.float64 if dtype == _lib.F64 else np.float32
+    outputs = tuple(outputs)
+    if not outputs or any(k not in _ROLLOUT_OUT for k in outputs):
+        raise ValueError(f"rollout_batch: outputs must name at least one of {_ROLLOUT_OUT} (got {outputs})")
+    x0 = np.asarray(x0, dtype=npdt)
+    if x0.ndim != 3 or x0.shape[0] != bt or x0.shape[2] != n:
+        raise ValueError("rollout_batch: x0 is (batch, S, n)")
+    S = x0.shape[1]
+    flat = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a, dtype=npdt)).reshape(-1)
+    mat = lambda a: None if a is None else to_abi(np.asarray(a, dtype=npdt)).reshape(-1)
+
+    def sized(name, a, size):
+        if a is not None and a.size != size:
+            raise ValueError(f"rollout_batch: {name} has {a.size} elements, expected {size}")
+        return a
+
+    kab, kq = (N - 1 if tvAB else 1), (N - 1 if tvQR else 1)
+    ins = dict(A=mat(b.A), B=mat(b.B), c=sized("c", flat(b.c), bt * kab * n),
+               K=sized("K", mat(K), bt * (N - 1) * m * n), d=sized("d", flat(d), bt * (N - 1) * m))
+    cost = dict.fromkeys(("Q", "R", "Qf", "M", "q", "r", "qf"))
+    if "J" in outputs:
+        cost.update(Q=mat(b.Q), R=mat(b.R), Qf=mat(b.Qf), M=sized("M", mat(b.M), bt * kq * m * n),
+                    q=sized("q", flat(b.q), bt * kq * n), r=sized("r", flat(b.r), bt * kq * m),
+                    qf=sized("qf", flat(b.qf), bt * n))
+    scn = dict(x0=flat(x0), alpha=sized("alpha", flat(alpha), bt * S), w=sized("w", flat(w), bt * S * (N - 1) * n),
+               u_lo=sized("u_lo", flat(u_lo), bt * m), u_hi=sized("u_hi", flat(u_hi), bt * m))
+    sizes = dict(X=bt * S * N * n, U=bt * S * (N - 1) * m, J=bt * S)
+    out = {k: np.zeros(sizes[k], npdt) for k in outputs}
+    p = lambda a: None if a is None else a.ctypes.data
+    ct = _lib.DpCost(*[p(cost[k]) for k in ("Q", "R", "Qf", "M", "q", "r", "qf")])
+    sc = _lib.DpScenarios(S, *[p(scn[k]) for k in ("x0", "alpha", "w", "u_lo", "u_hi")],
+                          *[p(out.get(k)) for k in _ROLLOUT_OUT])
+    desc = _lib.DpDesc(n, m, N, dtype, bt, 0, 0, tvAB, tvQR)
+    rc = _lib.check(_lib.load().lqrx_dp_rollout_host(
+        C.byref(desc), *[p(ins[k]) for k in ("A", "B", "c", "K", "d")],
+        C.byref(ct) if "J" in outputs else None, C.byref(sc)))
+    shapes = dict(X=(bt, S, N, n), U=(bt, S, N - 1, m), J=(bt, S))
+    res = {k: out[k].reshape(shapes[k]) for k in outputs}
+    res["rc"] = rc
+    return res
+
+
+def dp_rollout_device(t: dict, N: int, K, d, sc: dict, stream: int | None = None, out: dict | None = None) -> dict:
+    """Device-pointer entry point of the scenario rollout (lqrx_dp_rollout) on torch tensors already
+    in ABI layout (flat, layout 0), in the manner of dp_solve_device.
+
+    t: the problem — tensors A, B, optionally c, and for J the cost Q, R, Qf and optionally M, q, r, qf;
+    ints n, m, batch and optional tv_AB / tv_QR.  K, d: the solve's gains and feedforward (d may be
+    None: zero).  sc: S, tensor x0 (n·S·batch) and optionally alpha (S·batch), w (n·(N−1)·S·batch),
+    u_lo, u_hi (m·batch); "outputs" names which of X, U, J to form (default all three).  `out` may
+    hold preallocated X, U, J.  Returns the dict of output tensors (trajectory t = b·S + j: X
+    n·N per trajectory, U m·(N−1), J one element) and rc.  `stream` is a raw hipStream_t; None = the
+    null stream, synchronous.  The call allocates nothing inside the library."""
+    import torch
+
+    lib = _lib.load()
+    n, m, bt = t["n"], t["m"], t["batch"]
+    tdt = t["A"].dtype
+    dtype = _lib.F64 if tdt == torch.float64 else _lib.F32
+    dev = t["A"].device
+    S = int(sc["S"])
+    outputs = tuple(sc.get("outputs", _ROLLOUT_OUT))
+    if not outputs or any(k not in _ROLLOUT_OUT for k in outputs):
+        raise ValueError(f"dp_rollout_device: outputs must name at least one of {_ROLLOUT_OUT} (got {outputs})")
+    sizes = dict(X=bt * S * N * n, U=bt * S * (N - 1) * m, J=bt * S)
+    out = {} if out is None else out
+    for k in outputs:
+        if out.get(k) is None:
+            out[k] = torch.empty(sizes[k], dtype=tdt, device=dev)
+    p = lambda x: None if x is None else x.data_ptr()
+    ct = _lib.DpCost(*[p(t.get(k)) for k in ("Q", "R", "Qf", "M", "q", "r", "qf")])
+    scn = _lib.DpScenarios(S, *[p(sc.get(k)) for k in ("x0", "alpha", "w", "u_lo", "u_hi")],
+                           *[p(out[k]) if k in outputs else None for k in _ROLLOUT_OUT])
+    desc = _lib.DpDesc(n, m, N, dtype, bt, 0, 0, int(t.get("tv_AB", 0)), int(t.get("tv_QR", 0)))
+    vp = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+    rc = _lib.check(lib.lqrx_dp_rollout(C.byref(desc), vp(t["A"]), vp(t["B"]), vp(t.get("c")), vp(K), vp(d),
+                                        C.byref(ct) if "J" in outputs else None, C.byref(scn),
+                                        C.c_void_p(stream) if stream else None))
+    res = {k: out[k] for k in outputs}
+    res["rc"] = rc
+    return res

@@ -315,6 +315,7 @@ __device__ __forceinline__ bool ns_refine(typename Tile<T>::acc (&X)[MT][MT],
     return false;
 }
 
+constexpr int imax(int a, int b) { return a > b ? a : b; }
 template <typename T, int NT, int MT> struct DpCfg {
     static constexpr int NP = NT * 16, MP = MT * 16;
     static constexpr int CS = MP + 2;                       // padded LDS column stride
@@ -325,6 +326,13 @@ template <typename T, int NT, int MT> struct DpCfg {
     static constexpr int QCS = NP + 2;                      // LDS-resident Q image: column stride
     static constexpr int QIMG = NP * QCS;
     static constexpr int KPL = (MP * NP + 63) / 64;         // K elements per lane (rollout)
+    // VAR_CANON sizes its work area by what the kernel uses: the exact sweep's image is [E | I]
+    // (aug_ldl_forward<T, MP, 0, CS>: AUGC — AUG above still counts the G columns of the [E | G | I]
+    // sweep that no variant runs any more, and is left as it is so that the other variants keep their
+    // LDS layout and code), K̃'s transpose image MP × NP at stride CS
+    static constexpr int AUGC = 2 * MP * CS + 64 + MP, KTI = NP * CS;
+    static constexpr int WORK_CANON = imax(imax(AUGC, ROLL), imax(SYM, KTI));
+    static constexpr int LDS_CANON = WORK_CANON + MP * CS;   // + the Sᵀ image (read once per knot), behind the work area
 };
 
 // Forward rollout  dynamic_programming.jl:66-70 :  u_k = −K_k x_k ; x_{k+1} = A x_k + B u_k.
@@ -709,8 +717,17 @@ __device__ __forceinline__ void dp_rollout_full(const DpArgs &a, int64_t b, T *l
 //                knot loop unless every s_k is asked for (a.p_all, uniform over the grid); one
 //                16-lane reduction of the running sums either way, so s_1 is the same bits in
 //                both modes.
+//   VAR_CANON  : input-canonical coordinates (plain kind, time-invariant, exact tile grid, m ≤ n, P_1
+//                only).  The tiles hold Ã = TᵀAT, R̃ = SᵀRS, Q̃, Q̃f from the set-up's
+//                workspace (lqrx_dp_canon.hip; T from the QR of B, S = B₁⁻¹), where B̃ = [I; 0]: no B
+//                and PB tiles, E = R̃ + P̃[0:m, 0:m] (one tile add), G = the first m rows of P̃Ã (PA's
+//                own tiles).  The ABI's gain is K = S·K̃·Tᵀ: K̃ᵀ by an LDS transpose, then two TN
+//                products; −GᵀK keeps K̃.  P_1 = T·P̃_1·Tᵀ after the loop.  The rollout is the generic
+//                one on A, B and the stored K.  A trajectory whose workspace flag is 0 returns at once.
+//   VAR_MASK   : the generic kernel behind a VAR_CANON launch: a trajectory whose flag is 1 returns at
+//                once, the others are solved as by the kernel without the bit.
 enum : int { VAR_NOSOLVE = 2, VAR_NOROLL = 4, VAR_NOKSTORE = 8, VAR_SWEEPONLY = 16, VAR_TV = 32,
-             VAR_LIN = 64, VAR_AFF = 128, VAR_CROSS = 256, VAR_VALUE = 512 };
+             VAR_LIN = 64, VAR_AFF = 128, VAR_CROSS = 256, VAR_VALUE = 512, VAR_CANON = 1024, VAR_MASK = 2048 };
 
 // Vector products with register tiles (VAR_LIN).  A vector v is read from its LDS image in
 // "row layout" (lane l, slot [i][r] = v[16i + Tile::row(l, r)], the rows a C-layout tile's
@@ -763,10 +780,13 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
     constexpr bool CROSS = (VAR & VAR_CROSS) != 0;
     constexpr bool VALUE = (VAR & VAR_VALUE) != 0;
     static_assert(!VALUE || CROSS, "VAR_VALUE extends VAR_LIN | VAR_AFF | VAR_CROSS");
+    constexpr bool CANON = (VAR & VAR_CANON) != 0, MASK = (VAR & VAR_MASK) != 0;
+    static_assert(!CANON || (FULL && !TV && !LIN && MT <= NT && !MASK), "VAR_CANON: plain, time-invariant, exact grid");
+    static_assert(!MASK || (!TV && !LIN), "VAR_MASK: the plain time-invariant kernel");
     // Q + AᵀPA in the shadow of the Newton–Schulz chain (PnShadow): time-invariant A only
     constexpr bool SHADOW = !TV && (VAR & (VAR_NOSOLVE | VAR_SWEEPONLY)) == 0;
     constexpr int NP = C::NP;
-    __shared__ T lds[C::LDS_ELEMS];
+    __shared__ T lds[CANON ? C::LDS_CANON : C::LDS_ELEMS];
     // p (NP), then w / d (MP); time-invariant q (NP), r (MP) images after them; VAR_AFF: one more
     // NP slot, the time-invariant c image
     constexpr int CIMG = TV ? NP + MP : 2 * (NP + MP);
@@ -780,6 +800,10 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
     const int lane = threadIdx.x;
     const int64_t b = blockIdx.x;
     if (b >= a.batch) return;
+    // VAR_CANON / VAR_MASK: the set-up's verdict on this trajectory (wave-uniform)
+    if constexpr (CANON || MASK) {
+        if ((DpCanonWs<T, NT, MT>::flags(a.M)[b] != 0) != CANON) return;
+    }
     const int n = a.n, m = a.m, N = a.N;
     const size_t nn = (size_t)n * n, nm = (size_t)n * m, mm = (size_t)m * m;
     // per-trajectory bases; time-varying fields hold N-1 knots (knot k at index k-1)
@@ -792,17 +816,29 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
 #endif
     const T *Ab = (const T *)a.A + b * nn * kAB, *Bb = (const T *)a.B + b * nm * kAB;
     const T *Qb = (const T *)a.Q + b * nn * kQR, *Rb = (const T *)a.R + b * mm * kQR;
-    const T *Qg = Qb;
+    const T *Qg = Qb;                                           // VAR_CANON: Q̃ of the workspace, below
     // cross term M_k (m×n): knot stride with Q, R
     const size_t sM = (CROSS && kQR > 1) ? nm : 0;
     const T *Mb = CROSS ? (const T *)a.M + b * nm * kQR : nullptr;
 
-    acc At[NT][NT], Bt[NT][MT], Rt[MT][MT], P[NT][NT];
+    acc At[NT][NT], Bt[CANON ? 1 : NT][MT], Rt[MT][MT], P[NT][NT];
+    acc Tt[CANON ? NT : 1][CANON ? NT : 1];                     // VAR_CANON: Tᵀ
     const size_t k0 = TV ? (size_t)(N - 2) : 0;                 // first backward knot k = N-1
-    tiles_load<T, NT, NT, FULL>(At, Ab + k0 * sA, n, n, n, lane, false);
-    tiles_load<T, NT, MT, FULL>(Bt, Bb + k0 * sB, n, m, n, lane, false);
-    tiles_load<T, MT, MT, FULL>(Rt, Rb + k0 * sR, m, m, m, lane, true);
-    tiles_load<T, NT, NT, FULL>(P, (const T *)a.Qf + b * nn, n, n, n, lane, false); // :58 P = Qf
+    if constexpr (CANON) {
+        using W = DpCanonWs<T, NT, MT>;
+        const T *wsb = W::block(a.M, a.batch, b);
+        Qg = wsb + W::oQ;
+        tiles_load<T, NT, NT, true>(At, wsb + W::oA, n, n, n, lane, false);
+        tiles_load<T, MT, MT, true>(Rt, wsb + W::oR, m, m, m, lane, false);
+        tiles_load<T, NT, NT, true>(P, wsb + W::oQf, n, n, n, lane, false);
+        tiles_load<T, NT, NT, true>(Tt, wsb + W::oTt, n, n, n, lane, false);
+        for (int e = lane; e < MP * MP; e += 64) lds[C::WORK_CANON + e % MP + (e / MP) * CS] = wsb[W::oSt + e];   // Sᵀ image
+    } else {
+        tiles_load<T, NT, NT, FULL>(At, Ab + k0 * sA, n, n, n, lane, false);
+        tiles_load<T, NT, MT, FULL>(Bt, Bb + k0 * sB, n, m, n, lane, false);
+        tiles_load<T, MT, MT, FULL>(Rt, Rb + k0 * sR, m, m, m, lane, true);
+        tiles_load<T, NT, NT, FULL>(P, (const T *)a.Qf + b * nn, n, n, n, lane, false); // :58 P = Qf
+    }
     if constexpr (!TV) {
         // zero-padded NP×NP image of Q (padding rows/cols 0, as tiles_load_lower)
         for (int e = lane; e < C::NP * C::NP; e += 64) {
@@ -961,8 +997,10 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
                 __syncthreads();                       // p̃ complete before the row-layout read
             }
         };
-        tiles_zero<T, NT, MT>(PB);
-        mma_tn<T, NT, NT, MT>(PB, P, Bt);                          // :38 PB = P B
+        if constexpr (!CANON) {
+            tiles_zero<T, NT, MT>(PB);
+            mma_tn<T, NT, NT, MT>(PB, P, Bt);                      // :38 PB = P B
+        }
         tiles_zero<T, NT, NT>(PA);
         mma_tn<T, NT, NT, NT>(PA, P, At);                          // :40 PA = P A
         if constexpr (AFF && !TV) aff_ptilde();
@@ -981,13 +1019,25 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
             tiles_load_lower<T, NT, FULL>(Pn, Qb + (size_t)(k - 1) * sQ, n, n, lane);
         }
         else tiles_lower_from_lds<T, NT>(Pn, qimg, C::QCS, lane);       // P_ ← Q (lower tiles)
+        if constexpr (CANON) {
+            // B̃ = [I; 0]: E = R̃ + P̃[0:m, 0:m], G = the first m rows of P̃Ã (no instruction)
 #pragma unroll
-        for (int i = 0; i < MT; ++i)
+            for (int i = 0; i < MT; ++i)
 #pragma unroll
-            for (int j = 0; j < MT; ++j) E[i][j] = Rt[i][j];
-        mma_tn<T, NT, MT, MT>(E, Bt, PB);                          // :39 E = R + B'PB
-        if constexpr (!CROSS) tiles_zero<T, MT, NT>(G);
-        mma_tn<T, NT, MT, NT>(G, Bt, PA);                          // :41 K = B'PA (+ M_k)
+                for (int j = 0; j < MT; ++j) E[i][j] = Rt[i][j] + P[i][j];
+#pragma unroll
+            for (int i = 0; i < MT; ++i)
+#pragma unroll
+                for (int j = 0; j < NT; ++j) G[i][j] = PA[i][j];
+        } else {
+#pragma unroll
+            for (int i = 0; i < MT; ++i)
+#pragma unroll
+                for (int j = 0; j < MT; ++j) E[i][j] = Rt[i][j];
+            mma_tn<T, NT, MT, MT>(E, Bt, PB);                      // :39 E = R + B'PB
+            if constexpr (!CROSS) tiles_zero<T, MT, NT>(G);
+            mma_tn<T, NT, MT, NT>(G, Bt, PA);                      // :41 K = B'PA (+ M_k)
+        }
         // :51 Q + A'PA (lower): independent of the solve.  Time-invariant A: issued in chunks in
         // the shadow of the Newton–Schulz chain below (PnShadow); time-varying: here, before
         // A_k leaves the tiles.
@@ -1088,7 +1138,9 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
             }
             tiles_zero<T, MT, NT>(Kt);
             mma_tn<T, MT, MT, NT>(Kt, Xi, G);                          // K = XᵀG = E⁻¹G
-            if constexpr ((VAR & VAR_NOKSTORE) == 0)
+            // VAR_CANON: K̃ to its LDS image here; the ABI's gain is formed from it behind −GᵀK, below
+            if constexpr (CANON) tiles_to_lds<T, MT, NT>(Kt, lds, CS, lane);
+            else if constexpr ((VAR & VAR_NOKSTORE) == 0)
                 tiles_store<T, MT, NT, FULL>(Kt, Kb + (size_t)(k - 1) * nm, m, n, m, lane);
             if constexpr (LIN) {
                 if constexpr (!TV) {
@@ -1139,6 +1191,27 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
             }
         }
         mma_tn_lower<T, MT, NT, true>(Pn, G, Kt);                  // :50-51 − GᵀK (= APB K)
+        if constexpr (CANON) {
+            // the ABI's gain K = S·K̃·Tᵀ, here where G and K̃ are dead: K̃ᵀ read back from the image (a TN
+            // product contracts rows), K̃Tᵀ = (K̃ᵀ)ᵀTᵀ, then S·(K̃Tᵀ) = (Sᵀ)ᵀ(K̃Tᵀ) with Sᵀ from its image
+            __builtin_amdgcn_sched_barrier(0);
+            __syncthreads();
+            acc KtT[NT][MT], KT[MT][NT], Ko[MT][NT], St[MT][MT];
+#pragma unroll
+            for (int i = 0; i < NT; ++i)
+#pragma unroll
+                for (int j = 0; j < MT; ++j)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        KtT[i][j][r] = lds[(j * 16 + tcol(lane)) + (i * 16 + Tile<T>::row(lane, r)) * CS];
+            tiles_zero<T, MT, NT>(KT);
+            mma_tn<T, NT, MT, NT>(KT, KtT, Tt);
+            tiles_from_lds<T, MT, MT>(St, lds + C::WORK_CANON, CS, lane);
+            tiles_zero<T, MT, NT>(Ko);
+            mma_tn<T, MT, MT, NT>(Ko, St, KT);
+            tiles_store<T, MT, NT, FULL>(Ko, Kb + (size_t)(k - 1) * nm, m, n, m, lane);
+            __syncthreads();                                       // the image is read: the symmetrize may write
+        }
         tiles_symmetrize_lower<T, NT>(Pn, lds, didx, lane);        // P_ exactly symmetric
 #pragma unroll
         for (int i = 0; i < NT; ++i)
@@ -1157,6 +1230,28 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
                 if (lane == 0) ((T *)a.vs)[(size_t)b * (size_t)N + (k - 1)] = sk;
             }
         }
+    }
+    if constexpr (CANON) {
+        // VAR_CANON's own tail (the statements below are every other variant's, as they were).  Its lane
+        // index is laundered, so that the lane-derived offsets of the stores and the rollout are formed
+        // here and not ahead of the knot loop, where they were live across it and spilled 17 VGPRs.
+        int le = lane;
+        asm volatile("" : "+v"(le));
+        // P_1 = T·P̃_1·Tᵀ = (Tᵀ)ᵀ(P̃_1ᵀTᵀ), exactly symmetric as every P_ of the loop is
+        acc PT[NT][NT];
+        tiles_zero<T, NT, NT>(PT);
+        mma_tn<T, NT, NT, NT>(PT, P, Tt);
+        tiles_zero<T, NT, NT>(P);
+        mma_tn<T, NT, NT, NT>(P, Tt, PT);
+        tiles_symmetrize_lower<T, NT>(P, lds, le);
+        tiles_store<T, NT, NT>(P, (T *)a.P + (size_t)b * nn, n, n, n, le);
+        if (a.info && le == 0) a.info[b] = info;
+        // make this wave's K stores visible to its own (other-lane) rollout loads
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        dp_rollout_full<T, NT, MT, LQRX_DP_KD, false, false>(a, b, lds, le);
+        return;
     }
     if (!a.p_all) tiles_store<T, NT, NT>(P, (T *)a.P + (size_t)b * nn, n, n, n, lane);
     if (a.info && lane == 0) a.info[b] = info;
@@ -1775,6 +1870,11 @@ __global__ __launch_bounds__(256, 1) void dp_wg4_kernel(const DpArgs a)
     dp_rollout_wg4<T, MT, TV, LIN>(a, b, lds, w, lane);
 }
 
+// The launchers.  lqrx_dp_canon.hip includes this file for dp_riccati_kernel alone and leaves them
+// out: its VAR_CANON / VAR_MASK instantiations are compiled in that unit, so that this unit holds
+// the instantiations it always held (the compiler's code for a kernel was seen to depend on which
+// other instantiations share its module).
+#ifndef LQRX_DP_KERNELS_ONLY
 template <int MT>
 static hipError_t launch_wg4(const DpArgs &a, hipStream_t s)
 {
@@ -1860,8 +1960,18 @@ hipError_t dp_launch(const DpArgs &a_in, hipStream_t s)
     // or without linear terms (LQRX_DP_WG4=0 in the environment: the one-wave kernel, for A/B
     // runs and tests)
     static const bool wg4 = [] { const char *e = std::getenv("LQRX_DP_WG4"); return !(e && *e == '0'); }();
+    // plain time-invariant fp64 n = 32, m = 16, P_1 only: canonical coordinates (LQRX_DP_CANON=0 in
+    // the environment: the generic kernel, for A/B runs and tests).  The other exact grids stay
+    // generic.
+    static const bool canon = [] { const char *e = std::getenv("LQRX_DP_CANON"); return !(e && *e == '0'); }();
     return with_dtype(a.dtype, [&](auto t) {
         using T = decltype(t);
+        if constexpr (std::is_same_v<T, double>)
+            if (canon && kind == DP_PLAIN && !a.tv_AB && !a.tv_QR && !a.p_all && a.layout == 0 && a.n == 32 && a.m == 16) {
+                bool ran = false;                    // false: the pool had no workspace — the generic launch
+                const hipError_t e = dp_canon_launch(a, s, &ran);
+                if (ran || e != hipSuccess) return e;
+            }
         if (nt <= 1 && mt <= 1) return launch_dp_tv<T, 1, 1>(a, kind, s);
         if (nt <= 2 && mt <= 1) return launch_dp_tv<T, 2, 1>(a, kind, s);
         if (nt <= 2 && mt <= 2) return launch_dp_tv<T, 2, 2>(a, kind, s);
@@ -1920,5 +2030,7 @@ hipError_t dp_value_cost_launch(const DpArgs &a, void *J, hipStream_t s)
     else hipLaunchKernelGGL((dp_value_cost_kernel<float>), grid, block, 0, s, a, (float *)J);
     return hipGetLastError();
 }
+
+#endif // LQRX_DP_KERNELS_ONLY
 
 } // namespace lqrx

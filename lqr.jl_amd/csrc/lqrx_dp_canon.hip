@@ -1,0 +1,217 @@
+// lqrx_dp_canon.hip — set-up of the input-canonical form of a time-invariant LQR problem
+// ("canonical coordinates"), one wavefront per trajectory.
+//
+// Householder QR of B (n×m, m ≤ n, exact tile grids):  TᵀB = [B₁; 0], T orthogonal, B₁ upper
+// triangular, S = B₁⁻¹.  In x̃ = Tᵀx, ũ = B₁u the problem reads
+//   Ã = TᵀAT,  B̃ = [I_m; 0],  Q̃ = TᵀQT,  Q̃f = TᵀQfT,  R̃ = SᵀRS
+// and P̃_k = TᵀP_kT obeys the same recursion with BᵀPB, BᵀPA reduced to sub-blocks of P̃, P̃Ã
+// (dp_riccati_kernel, VAR_CANON).  The kernel writes Ã, Q̃, Q̃f, Tᵀ (n² each), R̃, Sᵀ (m² each) of
+// every trajectory and one flag per trajectory into the launch's workspace (DpCanonWs):
+// flag = 1, canonical applies;  0, it does not — a reflector met a zero column (rank-deficient
+// B), a non-finite value, or κ∞(B₁) = ‖B₁‖∞‖S‖∞ above the bound — and the trajectory is left to
+// the generic kernel (VAR_MASK), which the launcher runs behind the canonical one.
+//
+// The reflectors run on the augmented matrix [B | I] (n × (m + n)), one column per lane in
+// registers: after the m steps the first m lanes hold B₁ and the other n hold Tᵀ.  Reflector j's
+// vector is lane j's column, broadcast by v_readlane.  The congruences are TN MFMA products on
+// C-layout tiles (lqrx_tile.h); Q̃, Q̃f and R̃ are made exactly symmetric from their lower triangle.
+// Symmetric Q, Qf and R are assumed, as include/lqrx.h states them: the generic kernel mirrors Q's
+// lower triangle too, but reads Qf and R in full, so for a non-symmetric Qf or R the two paths would
+// solve different problems.
+//
+// This unit also holds the VAR_CANON and VAR_MASK instantiations of dp_riccati_kernel: it includes
+// lqrx_dp.hip for the kernel template alone (LQRX_DP_KERNELS_ONLY leaves that file's launchers out),
+// so that lqrx_dp.hip's own module keeps the instantiations, and with them the code, it always had.
+#define LQRX_DP_KERNELS_ONLY
+#include "lqrx_dp.hip"
+
+namespace lqrx {
+
+template <typename T, int NT, int MT>
+__global__ __launch_bounds__(64) void dp_canon_prep_kernel(const DpArgs a, void *wsv, T kappa_max)
+{
+    using acc = typename Tile<T>::acc;
+    using W = DpCanonWs<T, NT, MT>;
+    constexpr int NP = 16 * NT, MP = 16 * MT, NC = MP + NP;
+    constexpr int TS = NP + 2, SS = MP + 2;              // image column strides
+    static_assert(NC <= 64 && MP <= NP, "one column of [B | I] per lane");
+    __shared__ T timg[NP * TS];                          // Tᵀ, later the symmetrize image
+    __shared__ T bimg[MP * SS], simg[MP * SS];           // B₁, S
+
+    const int lane = threadIdx.x;
+    const int64_t b = blockIdx.x;
+    if (b >= a.batch) return;
+    constexpr size_t nn = (size_t)NP * NP, nm = (size_t)NP * MP, mm = (size_t)MP * MP;
+    const T *Bb = (const T *)a.B + b * nm;
+    int32_t *flag = W::flags(wsv) + b;
+    T *ws = W::block(wsv, a.batch, b);
+
+    // column `lane` of [B | I]
+    T x[NP];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+        if (lane < MP) x[i] = Bb[i + (size_t)lane * NP];
+        else x[i] = (lane - MP == i) ? (T)1 : (T)0;
+    }
+    bool deficient = false;
+#pragma unroll
+    for (int j = 0; j < MP; ++j) {
+        // H_j = I − τ v vᵀ on rows j …: v from column j (LAPACK's larfg: v_j = 1, H_j x = β e_j)
+        T v[NP];
+        T ss = (T)0;
+#pragma unroll
+        for (int i = j; i < NP; ++i) {
+            v[i] = readlane(x[i], j);
+            ss = fma(v[i], v[i], ss);
+        }
+        const T alpha = v[j];
+        const bool zero = !(ss > (T)0);
+        deficient = deficient || zero;
+        const T beta = -copysign(sqrt(ss), alpha);
+        const T tau = zero ? (T)0 : (beta - alpha) / beta;
+        const T sc = zero ? (T)0 : (T)1 / (alpha - beta);
+        T w = x[j];
+#pragma unroll
+        for (int i = j + 1; i < NP; ++i) {
+            v[i] *= sc;
+            w = fma(v[i], x[i], w);
+        }
+        w *= tau;
+        x[j] -= w;
+#pragma unroll
+        for (int i = j + 1; i < NP; ++i) x[i] = fma(-w, v[i], x[i]);
+    }
+    // images: B₁ (upper triangle; below it zero), Tᵀ
+    if (lane < MP) {
+#pragma unroll
+        for (int i = 0; i < MP; ++i) bimg[i + lane * SS] = i <= lane ? x[i] : (T)0;
+    } else if (lane < NC) {
+#pragma unroll
+        for (int i = 0; i < NP; ++i) timg[i + (lane - MP) * TS] = x[i];
+    }
+    __syncthreads();
+    // S = B₁⁻¹ by back substitution, column `lane` (rows past the column come out zero)
+    T s[MP];
+    const int c = lane < MP ? lane : 0;
+#pragma unroll
+    for (int i = MP - 1; i >= 0; --i) {
+        T r = (i == c) ? (T)1 : (T)0;
+#pragma unroll
+        for (int k = i + 1; k < MP; ++k) r = fma(-bimg[i + k * SS], s[k], r);
+        s[i] = r / bimg[i + i * SS];
+    }
+    if (lane < MP) {
+#pragma unroll
+        for (int i = 0; i < MP; ++i) simg[i + lane * SS] = s[i];
+    }
+    __syncthreads();
+    // κ∞(B₁) = ‖B₁‖∞‖S‖∞ from the row sums (row `lane`)
+    T rb = (T)0, rs = (T)0;
+    if (lane < MP) {
+#pragma unroll
+        for (int k = 0; k < MP; ++k) {
+            rb += fabs(bimg[lane + k * SS]);
+            rs += fabs(simg[lane + k * SS]);
+        }
+    }
+    const bool finite = __all((rb + rs) < (T)INFINITY);                 // false for inf and NaN
+    const T kappa = wave_max(rb) * wave_max(rs);
+    const bool ok = !deficient && finite && kappa <= kappa_max;
+    if (lane == 0) *flag = ok ? 1 : 0;
+    if (!ok) return;                                                    // wave-uniform
+
+    // T (transposed read of the Tᵀ image) and S in tiles
+    acc Tn[NT][NT], Sn[MT][MT];
+#pragma unroll
+    for (int i = 0; i < NT; ++i)
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                Tn[i][j][r] = timg[(j * 16 + tcol(lane)) + (i * 16 + Tile<T>::row(lane, r)) * TS];
+    tiles_from_lds<T, MT, MT>(Sn, simg, SS, lane);
+    __syncthreads();                                                    // timg is free from here
+    // Tᵀ and Sᵀ: T's and S's tiles stored transposed
+#pragma unroll
+    for (int i = 0; i < NT; ++i)
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                ws[W::oTt + (j * 16 + tcol(lane)) + (size_t)(i * 16 + Tile<T>::row(lane, r)) * NP] = Tn[i][j][r];
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < MT; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                ws[W::oSt + (j * 16 + tcol(lane)) + (size_t)(i * 16 + Tile<T>::row(lane, r)) * MP] = Sn[i][j][r];
+
+    acc X[NT][NT], Y[NT][NT], Z[NT][NT];
+    // Ã = TᵀAT = (AᵀT)ᵀT
+    tiles_load<T, NT, NT, true>(X, (const T *)a.A + b * nn, NP, NP, NP, lane, false);
+    tiles_zero<T, NT, NT>(Y);
+    mma_tn<T, NT, NT, NT>(Y, X, Tn);
+    tiles_zero<T, NT, NT>(Z);
+    mma_tn<T, NT, NT, NT>(Z, Y, Tn);
+    tiles_store<T, NT, NT, true>(Z, ws + W::oA, NP, NP, NP, lane);
+    // Q̃ = Tᵀ(QT), Q the symmetric matrix that the generic kernel reads: the lower triangle, mirrored
+    tiles_load_lower<T, NT, true>(X, (const T *)a.Q + b * nn, NP, NP, lane);
+    tiles_symmetrize_lower<T, NT>(X, timg, lane);
+    tiles_zero<T, NT, NT>(Y);
+    mma_tn<T, NT, NT, NT>(Y, X, Tn);
+    tiles_zero<T, NT, NT>(Z);
+    mma_tn<T, NT, NT, NT>(Z, Tn, Y);
+    tiles_symmetrize_lower<T, NT>(Z, timg, lane);
+    tiles_store<T, NT, NT, true>(Z, ws + W::oQ, NP, NP, NP, lane);
+    // Q̃f = Tᵀ(QfᵀT)
+    tiles_load<T, NT, NT, true>(X, (const T *)a.Qf + b * nn, NP, NP, NP, lane, false);
+    tiles_zero<T, NT, NT>(Y);
+    mma_tn<T, NT, NT, NT>(Y, X, Tn);
+    tiles_zero<T, NT, NT>(Z);
+    mma_tn<T, NT, NT, NT>(Z, Tn, Y);
+    tiles_symmetrize_lower<T, NT>(Z, timg, lane);
+    tiles_store<T, NT, NT, true>(Z, ws + W::oQf, NP, NP, NP, lane);
+    // R̃ = Sᵀ(RᵀS)
+    acc Rm[MT][MT], RS[MT][MT], Rc[MT][MT];
+    tiles_load<T, MT, MT, true>(Rm, (const T *)a.R + b * mm, MP, MP, MP, lane, false);
+    tiles_zero<T, MT, MT>(RS);
+    mma_tn<T, MT, MT, MT>(RS, Rm, Sn);
+    tiles_zero<T, MT, MT>(Rc);
+    mma_tn<T, MT, MT, MT>(Rc, Sn, RS);
+    tiles_symmetrize_lower<T, MT>(Rc, timg, lane);
+    tiles_store<T, MT, MT, true>(Rc, ws + W::oR, MP, MP, MP, lane);
+}
+
+// The canonical-form solve: the set-up fills a pool workspace, the VAR_CANON kernel solves the
+// trajectories it admitted, the generic kernel behind it (VAR_MASK) the ones it did not — an empty
+// launch when there are none.  Stream-ordered throughout: no host synchronisation.  Where the pool
+// cannot give the workspace (36 KB per trajectory) nothing is launched and *ran is false.
+hipError_t dp_canon_launch(const DpArgs &a_in, hipStream_t s, bool *ran)
+{
+    using W = DpCanonWs<double, 2, 1>;
+    void *ws = nullptr;
+    *ran = false;
+    if (scratch_alloc(&ws, W::bytes(a_in.batch), s) != hipSuccess) {
+        (void)hipGetLastError();                     // the allocation's error is not the caller's
+        return hipSuccess;
+    }
+    *ran = true;
+    DpArgs a = a_in;
+    a.M = ws;
+    dim3 grid((unsigned)a.batch), block(64);
+    hipLaunchKernelGGL((dp_canon_prep_kernel<double, 2, 1>), grid, block, 0, s, a, ws, DP_CANON_KAPPA_F64);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL((dp_riccati_kernel<double, 2, 1, 2, VAR_CANON, true>), grid, block, 0, s, a);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL((dp_riccati_kernel<double, 2, 1, 2, VAR_MASK, true>), grid, block, 0, s, a);
+        e = hipGetLastError();
+    }
+    const hipError_t f = scratch_free(ws, s);
+    return e != hipSuccess ? e : f;
+}
+
+} // namespace lqrx

@@ -197,25 +197,26 @@ struct NsNoShadow {
     template <int C> __device__ __forceinline__ void chunk() const {}
 };
 // the K-independent part of P_: Pn += AᵀPA (lower tiles), mma_tn_lower's MFMAs in its order,
-// cut into NCH = 4·MT + 2 chunks (per accumulator the MFMA order is mma_tn_lower's: same bits)
-template <typename T, int NT, int MT> struct PnShadow {
+// cut into NCH = 4·MT + 2 chunks (per accumulator the MFMA order is mma_tn_lower's: same bits).
+// KT: the product's row tiles — NT, or VAR_PREFB's NT − MT (A₂ᵀ(P̃₂₂A₂): half the MFMAs per chunk)
+template <typename T, int NT, int MT, int KT = NT> struct PnShadow {
     using acc = typename Tile<T>::acc;
-    static constexpr int NCH = 4 * MT + 2, TOT = mma_tn_lower_count<T, NT, NT>();
+    static constexpr int NCH = 4 * MT + 2, TOT = mma_tn_lower_count<T, KT, NT>();
     static constexpr int CH = (TOT + NCH - 1) / NCH;
     acc (&Pn)[NT][NT];
-    const acc (&At)[NT][NT];
-    const acc (&PA)[NT][NT];
+    const acc (&At)[KT][NT];
+    const acc (&PA)[KT][NT];
     template <int C> __device__ __forceinline__ void chunk() const
     {
         // pinned: the scheduler must not move the chunk off the wait it is there to cover
         __builtin_amdgcn_sched_barrier(0);
-        mma_tn_lower_range<T, NT, NT, C * CH, (C + 1) * CH>(Pn, At, PA);
+        mma_tn_lower_range<T, KT, NT, C * CH, (C + 1) * CH>(Pn, At, PA);
         __builtin_amdgcn_sched_barrier(0);
     }
     // chunks [B, E) unpinned
     template <int B, int E> __device__ __forceinline__ void range() const
     {
-        mma_tn_lower_range<T, NT, NT, B * CH, E * CH>(Pn, At, PA);
+        mma_tn_lower_range<T, KT, NT, B * CH, E * CH>(Pn, At, PA);
     }
     // the chunks ns_refine did not issue: `done` is 0 (not called), 1, 4·MT + 1 or NCH
     __device__ __forceinline__ void rest(int done) const
@@ -724,10 +725,20 @@ __device__ __forceinline__ void dp_rollout_full(const DpArgs &a, int64_t b, T *l
 //                own tiles).  The ABI's gain is K = S·K̃·Tᵀ: K̃ᵀ by an LDS transpose, then two TN
 //                products; −GᵀK keeps K̃.  P_1 = T·P̃_1·Tᵀ after the loop.  The rollout is the generic
 //                one on A, B and the stored K.  A trajectory whose workspace flag is 0 returns at once.
-//   VAR_MASK   : the generic kernel behind a VAR_CANON launch: a trajectory whose flag is 1 returns at
-//                once, the others are solved as by the kernel without the bit.
+//                (Flag 1 is its own; 2 is VAR_PREFB's, 0 VAR_MASK's.)
+//   VAR_MASK   : the generic kernel behind a VAR_CANON launch: a trajectory whose flag is not 0 returns
+//                at once, the others are solved as by the kernel without the bit.
+//   VAR_PREFB  : on top of VAR_CANON, for the trajectories the set-up flags 2 (κ∞(B₁) under
+//                DP_PREFB_KAPPA_F64): the deadbeat pre-feedback ũ = v − A₁x̃ (A₁, A₂ the first
+//                m and the other rows of Ã) leaves the dynamics [0; A₂] and the cost Q′ = Q̃ + A₁ᵀR̃A₁,
+//                M′ = −R̃A₁, R̃, with the same P̃_k and Ẽ.  Only A₂'s tiles are held; the one product
+//                [P̃₁₂; P̃₂₂]·A₂ gives G = M′ + P̃₁₂A₂ (M′, in the registers A₁ had, is the accumulators'
+//                start) and P̃₂₂A₂; Q′ + A₂ᵀ(P̃₂₂A₂) is PnShadow's shorter product; the ABI's gain is
+//                K = S·K_v·Tᵀ + C, C = S·A₁·Tᵀ of the workspace the accumulators' start, loaded every
+//                knot (cache-resident) behind −GᵀK_v.  80 MFMAs per knot where VAR_CANON has 108.
 enum : int { VAR_NOSOLVE = 2, VAR_NOROLL = 4, VAR_NOKSTORE = 8, VAR_SWEEPONLY = 16, VAR_TV = 32,
-             VAR_LIN = 64, VAR_AFF = 128, VAR_CROSS = 256, VAR_VALUE = 512, VAR_CANON = 1024, VAR_MASK = 2048 };
+             VAR_LIN = 64, VAR_AFF = 128, VAR_CROSS = 256, VAR_VALUE = 512, VAR_CANON = 1024, VAR_MASK = 2048,
+             VAR_PREFB = 4096 };
 
 // Vector products with register tiles (VAR_LIN).  A vector v is read from its LDS image in
 // "row layout" (lane l, slot [i][r] = v[16i + Tile::row(l, r)], the rows a C-layout tile's
@@ -783,6 +794,9 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
     constexpr bool CANON = (VAR & VAR_CANON) != 0, MASK = (VAR & VAR_MASK) != 0;
     static_assert(!CANON || (FULL && !TV && !LIN && MT <= NT && !MASK), "VAR_CANON: plain, time-invariant, exact grid");
     static_assert(!MASK || (!TV && !LIN), "VAR_MASK: the plain time-invariant kernel");
+    constexpr bool PREFB = (VAR & VAR_PREFB) != 0;
+    static_assert(!PREFB || (CANON && MT < NT), "VAR_PREFB extends VAR_CANON, m < n");
+    constexpr int AK = PREFB ? NT - MT : NT;                    // A's row tiles in registers (VAR_PREFB: A₂ alone)
     // Q + AᵀPA in the shadow of the Newton–Schulz chain (PnShadow): time-invariant A only
     constexpr bool SHADOW = !TV && (VAR & (VAR_NOSOLVE | VAR_SWEEPONLY)) == 0;
     constexpr int NP = C::NP;
@@ -800,9 +814,10 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
     const int lane = threadIdx.x;
     const int64_t b = blockIdx.x;
     if (b >= a.batch) return;
-    // VAR_CANON / VAR_MASK: the set-up's verdict on this trajectory (wave-uniform)
+    // VAR_CANON / VAR_MASK: the set-up's verdict on this trajectory (wave-uniform), each kernel of
+    // the launch takes the trajectories of its own flag value
     if constexpr (CANON || MASK) {
-        if ((DpCanonWs<T, NT, MT>::flags(a.M)[b] != 0) != CANON) return;
+        if (DpCanonWs<T, NT, MT>::flags(a.M)[b] != (PREFB ? 2 : CANON ? 1 : 0)) return;
     }
     const int n = a.n, m = a.m, N = a.N;
     const size_t nn = (size_t)n * n, nm = (size_t)n * m, mm = (size_t)m * m;
@@ -821,14 +836,21 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
     const size_t sM = (CROSS && kQR > 1) ? nm : 0;
     const T *Mb = CROSS ? (const T *)a.M + b * nm * kQR : nullptr;
 
-    acc At[NT][NT], Bt[CANON ? 1 : NT][MT], Rt[MT][MT], P[NT][NT];
+    acc At[AK][NT], Bt[CANON ? 1 : NT][MT], Rt[MT][MT], P[NT][NT];
     acc Tt[CANON ? NT : 1][CANON ? NT : 1];                     // VAR_CANON: Tᵀ
+    acc Mp[PREFB ? MT : 1][PREFB ? NT : 1];                     // VAR_PREFB: M′
+    const T *Cg = nullptr;                                      // VAR_PREFB: C of the workspace
     const size_t k0 = TV ? (size_t)(N - 2) : 0;                 // first backward knot k = N-1
     if constexpr (CANON) {
         using W = DpCanonWs<T, NT, MT>;
         const T *wsb = W::block(a.M, a.batch, b);
-        Qg = wsb + W::oQ;
-        tiles_load<T, NT, NT, true>(At, wsb + W::oA, n, n, n, lane, false);
+        Qg = wsb + W::oQ;                                       // VAR_PREFB: the set-up wrote Q′ there
+        if constexpr (PREFB) {
+            tiles_load<T, AK, NT, true>(At, wsb + W::oA + MP, n - m, n, n, lane, false);   // rows m … of Ã
+            tiles_load<T, MT, NT, true>(Mp, wsb + W::oMp, m, n, m, lane, false);
+            Cg = wsb + W::oC;
+        } else
+            tiles_load<T, NT, NT, true>(At, wsb + W::oA, n, n, n, lane, false);
         tiles_load<T, MT, MT, true>(Rt, wsb + W::oR, m, m, m, lane, false);
         tiles_load<T, NT, NT, true>(P, wsb + W::oQf, n, n, n, lane, false);
         tiles_load<T, NT, NT, true>(Tt, wsb + W::oTt, n, n, n, lane, false);
@@ -902,7 +924,7 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
     for (int r = 0; r < 4; ++r) asm volatile("" : "+v"(didx[r]));
 
     for (int k = N - 1; k >= 1; --k) { // :61
-        acc PB[NT][MT], E[MT][MT], PA[NT][NT], G[MT][NT], Pn[NT][NT];
+        acc PB[NT][MT], E[MT][MT], PA[AK][NT], G[MT][NT], Pn[NT][NT];   // VAR_PREFB: PA = P̃₂₂A₂, its rows m …
         // column layout; time-varying: issued ahead of the MFMAs, time-invariant: read from
         // the LDS images where they are used (no registers held across the knot)
         T qv[LIN ? NT : 1], rv[LIN ? MT : 1];
@@ -1001,8 +1023,28 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
             tiles_zero<T, NT, MT>(PB);
             mma_tn<T, NT, NT, MT>(PB, P, Bt);                      // :38 PB = P B
         }
-        tiles_zero<T, NT, NT>(PA);
-        mma_tn<T, NT, NT, NT>(PA, P, At);                          // :40 PA = P A
+        if constexpr (PREFB) {
+            // [P̃₁₂; P̃₂₂]·A₂ in mma_tn's order, its first m rows onto M′: G = M′ + P̃₁₂A₂, PA = P̃₂₂A₂
+#pragma unroll
+            for (int i = 0; i < MT; ++i)
+#pragma unroll
+                for (int j = 0; j < NT; ++j) G[i][j] = Mp[i][j];
+            tiles_zero<T, AK, NT>(PA);
+#pragma unroll
+            for (int kk = 0; kk < AK; ++kk)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+#pragma unroll
+                    for (int i = 0; i < NT; ++i)
+#pragma unroll
+                        for (int j = 0; j < NT; ++j) {
+                            acc &D = i < MT ? G[i][j] : PA[i < MT ? 0 : i - MT][j];
+                            D = Tile<T>::mma(P[MT + kk][i][r], At[kk][j][r], D);
+                        }
+        } else {
+            tiles_zero<T, AK, NT>(PA);
+            mma_tn<T, NT, NT, NT>(PA, P, At);                      // :40 PA = P A
+        }
         if constexpr (AFF && !TV) aff_ptilde();
         // VAR_CROSS: G starts from M_k (zero padded past m, n).  The loads are issued here, beside
         // Q's, and land behind the E product; issued ahead of PB / PA they held G's registers across
@@ -1025,10 +1067,12 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
             for (int i = 0; i < MT; ++i)
 #pragma unroll
                 for (int j = 0; j < MT; ++j) E[i][j] = Rt[i][j] + P[i][j];
+            if constexpr (!PREFB) {
 #pragma unroll
-            for (int i = 0; i < MT; ++i)
+                for (int i = 0; i < MT; ++i)
 #pragma unroll
-                for (int j = 0; j < NT; ++j) G[i][j] = PA[i][j];
+                    for (int j = 0; j < NT; ++j) G[i][j] = PA[i][j];
+            }
         } else {
 #pragma unroll
             for (int i = 0; i < MT; ++i)
@@ -1041,9 +1085,9 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
         // :51 Q + A'PA (lower): independent of the solve.  Time-invariant A: issued in chunks in
         // the shadow of the Newton–Schulz chain below (PnShadow); time-varying: here, before
         // A_k leaves the tiles.
-        const PnShadow<T, NT, MT> pn_shadow{Pn, At, PA};
+        const PnShadow<T, NT, MT, AK> pn_shadow{Pn, At, PA};        // VAR_PREFB: Q′ + A₂ᵀ(P̃₂₂A₂)
         int pn_done = 0;
-        if constexpr (!SHADOW) mma_tn_lower<T, NT, NT>(Pn, At, PA);
+        if constexpr (!SHADOW) mma_tn_lower<T, AK, NT>(Pn, At, PA);
         // linear terms, first half (time-varying: before A_k, B_k leave the tiles; time-
         // invariant: after the solve, where fewer registers are live): w = r + Bᵀp, Aᵀp partials
         T w[LIN ? MT : 1], ap[LIN ? NT : 1];
@@ -1190,13 +1234,26 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
                 __syncthreads();
             }
         }
+        // VAR_PREFB: C into the ABI gain's accumulators, issued here so that the (cache-resident) load
+        // lands under −GᵀK_v and K_vTᵀ.  The workspace holds C as the lanes hold its tiles (tile, lane,
+        // register), 32 B per lane and tile; the lane index is laundered so that the offset is formed
+        // per knot and not held across the loop.
+        acc Ko[CANON ? MT : 1][CANON ? NT : 1];
+        if constexpr (PREFB) {
+            int lc = lane;
+            asm volatile("" : "+v"(lc));
+#pragma unroll
+            for (int i = 0; i < MT; ++i)
+#pragma unroll
+                for (int j = 0; j < NT; ++j) Ko[i][j] = *(const acc *)(Cg + ((size_t)((i * NT + j) * 64 + lc)) * 4);
+        }
         mma_tn_lower<T, MT, NT, true>(Pn, G, Kt);                  // :50-51 − GᵀK (= APB K)
         if constexpr (CANON) {
             // the ABI's gain K = S·K̃·Tᵀ, here where G and K̃ are dead: K̃ᵀ read back from the image (a TN
             // product contracts rows), K̃Tᵀ = (K̃ᵀ)ᵀTᵀ, then S·(K̃Tᵀ) = (Sᵀ)ᵀ(K̃Tᵀ) with Sᵀ from its image
             __builtin_amdgcn_sched_barrier(0);
             __syncthreads();
-            acc KtT[NT][MT], KT[MT][NT], Ko[MT][NT], St[MT][MT];
+            acc KtT[NT][MT], KT[MT][NT], St[MT][MT];
 #pragma unroll
             for (int i = 0; i < NT; ++i)
 #pragma unroll
@@ -1207,7 +1264,7 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
             tiles_zero<T, MT, NT>(KT);
             mma_tn<T, NT, MT, NT>(KT, KtT, Tt);
             tiles_from_lds<T, MT, MT>(St, lds + C::WORK_CANON, CS, lane);
-            tiles_zero<T, MT, NT>(Ko);
+            if constexpr (!PREFB) tiles_zero<T, MT, NT>(Ko);       // VAR_PREFB: K = S·(K_vTᵀ) + C
             mma_tn<T, MT, MT, NT>(Ko, St, KT);
             tiles_store<T, MT, NT, FULL>(Ko, Kb + (size_t)(k - 1) * nm, m, n, m, lane);
             __syncthreads();                                       // the image is read: the symmetrize may write
@@ -1961,7 +2018,8 @@ hipError_t dp_launch(const DpArgs &a_in, hipStream_t s)
     // runs and tests)
     static const bool wg4 = [] { const char *e = std::getenv("LQRX_DP_WG4"); return !(e && *e == '0'); }();
     // plain time-invariant fp64 n = 32, m = 16, P_1 only: canonical coordinates (LQRX_DP_CANON=0 in
-    // the environment: the generic kernel, for A/B runs and tests).  The other exact grids stay
+    // the environment: the generic kernel, for A/B runs and tests; LQRX_DP_PREFB=0, read in
+    // dp_canon_launch: canonical without the pre-feedback tier).  The other exact grids stay
     // generic.
     static const bool canon = [] { const char *e = std::getenv("LQRX_DP_CANON"); return !(e && *e == '0'); }();
     return with_dtype(a.dtype, [&](auto t) {

@@ -9,7 +9,10 @@
 // every trajectory and one flag per trajectory into the launch's workspace (DpCanonWs):
 // flag = 1, canonical applies;  0, it does not — a reflector met a zero column (rank-deficient
 // B), a non-finite value, or κ∞(B₁) = ‖B₁‖∞‖S‖∞ above the bound — and the trajectory is left to
-// the generic kernel (VAR_MASK), which the launcher runs behind the canonical one.
+// the generic kernel (VAR_MASK), which the launcher runs behind the canonical one;  2, canonical
+// with the deadbeat pre-feedback (VAR_PREFB, lqrx_dp_prefb.hip), where κ∞(B₁) is also under
+// DP_PREFB_KAPPA_F64: for those the kernel writes Q′ = Q̃ + A₁ᵀR̃A₁ in Q̃'s place and, behind Sᵀ,
+// M′ = −R̃A₁ and C = S·A₁·Tᵀ (A₁ the first m rows of Ã), 36 MFMAs more per trajectory.
 //
 // The reflectors run on the augmented matrix [B | I] (n × (m + n)), one column per lane in
 // registers: after the m steps the first m lanes hold B₁ and the other n hold Tᵀ.  Reflector j's
@@ -28,7 +31,7 @@
 namespace lqrx {
 
 template <typename T, int NT, int MT>
-__global__ __launch_bounds__(64) void dp_canon_prep_kernel(const DpArgs a, void *wsv, T kappa_max)
+__global__ __launch_bounds__(64) void dp_canon_prep_kernel(const DpArgs a, void *wsv, T kappa_max, T kappa_pf)
 {
     using acc = typename Tile<T>::acc;
     using W = DpCanonWs<T, NT, MT>;
@@ -117,7 +120,8 @@ __global__ __launch_bounds__(64) void dp_canon_prep_kernel(const DpArgs a, void 
     const bool finite = __all((rb + rs) < (T)INFINITY);                 // false for inf and NaN
     const T kappa = wave_max(rb) * wave_max(rs);
     const bool ok = !deficient && finite && kappa <= kappa_max;
-    if (lane == 0) *flag = ok ? 1 : 0;
+    const bool pf = ok && kappa <= kappa_pf;                            // the pre-feedback tier (VAR_PREFB)
+    if (lane == 0) *flag = ok ? (pf ? 2 : 1) : 0;
     if (!ok) return;                                                    // wave-uniform
 
     // T (transposed read of the Tᵀ image) and S in tiles
@@ -147,6 +151,16 @@ __global__ __launch_bounds__(64) void dp_canon_prep_kernel(const DpArgs a, void 
             for (int r = 0; r < 4; ++r)
                 ws[W::oSt + (j * 16 + tcol(lane)) + (size_t)(i * 16 + Tile<T>::row(lane, r)) * MP] = Sn[i][j][r];
 
+    // R̃ = Sᵀ(RᵀS)
+    acc Rm[MT][MT], RS[MT][MT], Rc[MT][MT];
+    tiles_load<T, MT, MT, true>(Rm, (const T *)a.R + b * mm, MP, MP, MP, lane, false);
+    tiles_zero<T, MT, MT>(RS);
+    mma_tn<T, MT, MT, MT>(RS, Rm, Sn);
+    tiles_zero<T, MT, MT>(Rc);
+    mma_tn<T, MT, MT, MT>(Rc, Sn, RS);
+    tiles_symmetrize_lower<T, MT>(Rc, timg, lane);
+    tiles_store<T, MT, MT, true>(Rc, ws + W::oR, MP, MP, MP, lane);
+
     acc X[NT][NT], Y[NT][NT], Z[NT][NT];
     // Ã = TᵀAT = (AᵀT)ᵀT
     tiles_load<T, NT, NT, true>(X, (const T *)a.A + b * nn, NP, NP, NP, lane, false);
@@ -155,6 +169,47 @@ __global__ __launch_bounds__(64) void dp_canon_prep_kernel(const DpArgs a, void 
     tiles_zero<T, NT, NT>(Z);
     mma_tn<T, NT, NT, NT>(Z, Y, Tn);
     tiles_store<T, NT, NT, true>(Z, ws + W::oA, NP, NP, NP, lane);
+    // the pre-feedback tier's own data (wave-uniform branch), A₁ = the first m rows of Ã:
+    //   M′ = −R̃A₁ (R̃ exactly symmetric: R̃ᵀA₁),  R̃A₁ kept for Q′ below,
+    //   C = S·A₁·Tᵀ = S·(T₁ᵀA), T₁ the first m columns of T (A₁Tᵀ = T₁ᵀA·TTᵀ): from A's and T's tiles
+    //   as they stand, Sᵀ's tile a transposed read of the S image
+    acc A1[MT][NT], RA[MT][NT];
+    if (pf) {
+        acc Mn[MT][NT], T1[NT][MT], W1[MT][NT], Stt[MT][MT], Cc[MT][NT];
+        tiles_zero<T, MT, NT>(RA);
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int j = 0; j < NT; ++j) A1[i][j] = Z[i][j];
+        mma_tn<T, MT, MT, NT>(RA, Rc, A1);
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int j = 0; j < NT; ++j) Mn[i][j] = -RA[i][j];
+        tiles_store<T, MT, NT, true>(Mn, ws + W::oMp, MP, NP, MP, lane);
+#pragma unroll
+        for (int k = 0; k < NT; ++k)
+#pragma unroll
+            for (int i = 0; i < MT; ++i) T1[k][i] = Tn[k][i];
+        tiles_zero<T, MT, NT>(W1);
+        mma_tn<T, NT, MT, NT>(W1, T1, X);
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int j = 0; j < MT; ++j)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    Stt[i][j][r] = simg[(j * 16 + tcol(lane)) + (i * 16 + Tile<T>::row(lane, r)) * SS];
+        tiles_zero<T, MT, NT>(Cc);
+        mma_tn<T, MT, MT, NT>(Cc, Stt, W1);
+        // C as the lanes hold its tiles (tile, lane, register): the solve kernel reads 32 B per lane and tile
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int j = 0; j < NT; ++j)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) ws[W::oC + ((size_t)((i * NT + j) * 64 + lane)) * 4 + r] = Cc[i][j][r];
+    }
     // Q̃ = Tᵀ(QT), Q the symmetric matrix that the generic kernel reads: the lower triangle, mirrored
     tiles_load_lower<T, NT, true>(X, (const T *)a.Q + b * nn, NP, NP, lane);
     tiles_symmetrize_lower<T, NT>(X, timg, lane);
@@ -162,6 +217,7 @@ __global__ __launch_bounds__(64) void dp_canon_prep_kernel(const DpArgs a, void 
     mma_tn<T, NT, NT, NT>(Y, X, Tn);
     tiles_zero<T, NT, NT>(Z);
     mma_tn<T, NT, NT, NT>(Z, Tn, Y);
+    if (pf) mma_tn_lower<T, MT, NT>(Z, A1, RA);                         // Q′ = Q̃ + A₁ᵀ(R̃A₁), in Q̃'s place
     tiles_symmetrize_lower<T, NT>(Z, timg, lane);
     tiles_store<T, NT, NT, true>(Z, ws + W::oQ, NP, NP, NP, lane);
     // Q̃f = Tᵀ(QfᵀT)
@@ -172,21 +228,13 @@ __global__ __launch_bounds__(64) void dp_canon_prep_kernel(const DpArgs a, void 
     mma_tn<T, NT, NT, NT>(Z, Tn, Y);
     tiles_symmetrize_lower<T, NT>(Z, timg, lane);
     tiles_store<T, NT, NT, true>(Z, ws + W::oQf, NP, NP, NP, lane);
-    // R̃ = Sᵀ(RᵀS)
-    acc Rm[MT][MT], RS[MT][MT], Rc[MT][MT];
-    tiles_load<T, MT, MT, true>(Rm, (const T *)a.R + b * mm, MP, MP, MP, lane, false);
-    tiles_zero<T, MT, MT>(RS);
-    mma_tn<T, MT, MT, MT>(RS, Rm, Sn);
-    tiles_zero<T, MT, MT>(Rc);
-    mma_tn<T, MT, MT, MT>(Rc, Sn, RS);
-    tiles_symmetrize_lower<T, MT>(Rc, timg, lane);
-    tiles_store<T, MT, MT, true>(Rc, ws + W::oR, MP, MP, MP, lane);
 }
 
-// The canonical-form solve: the set-up fills a pool workspace, the VAR_CANON kernel solves the
-// trajectories it admitted, the generic kernel behind it (VAR_MASK) the ones it did not — an empty
-// launch when there are none.  Stream-ordered throughout: no host synchronisation.  Where the pool
-// cannot give the workspace (36 KB per trajectory) nothing is launched and *ran is false.
+// The canonical-form solve: the set-up fills a pool workspace and sorts the trajectories into three
+// tiers; the VAR_PREFB kernel solves those flagged 2, the VAR_CANON kernel those flagged 1, the
+// generic kernel behind them (VAR_MASK) the ones the set-up did not admit — over the same grid, each
+// an empty launch (16 µs) when it has none.  Stream-ordered throughout: no host synchronisation.  Where
+// the pool cannot give the workspace (44 KB per trajectory) nothing is launched and *ran is false.
 hipError_t dp_canon_launch(const DpArgs &a_in, hipStream_t s, bool *ran)
 {
     using W = DpCanonWs<double, 2, 1>;
@@ -200,8 +248,13 @@ hipError_t dp_canon_launch(const DpArgs &a_in, hipStream_t s, bool *ran)
     DpArgs a = a_in;
     a.M = ws;
     dim3 grid((unsigned)a.batch), block(64);
-    hipLaunchKernelGGL((dp_canon_prep_kernel<double, 2, 1>), grid, block, 0, s, a, ws, DP_CANON_KAPPA_F64);
+    // LQRX_DP_PREFB=0 in the environment (read once): no trajectory gets flag 2 — κ∞ ≥ 1 is above a
+    // zero bound — so the pre-feedback candidates go to the VAR_CANON kernel
+    static const bool prefb = [] { const char *e = std::getenv("LQRX_DP_PREFB"); return !(e && *e == '0'); }();
+    hipLaunchKernelGGL((dp_canon_prep_kernel<double, 2, 1>), grid, block, 0, s, a, ws, DP_CANON_KAPPA_F64,
+                       prefb ? DP_PREFB_KAPPA_F64 : 0.0);
     hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = dp_prefb_launch(a, s);
     if (e == hipSuccess) {
         hipLaunchKernelGGL((dp_riccati_kernel<double, 2, 1, 2, VAR_CANON, true>), grid, block, 0, s, a);
         e = hipGetLastError();

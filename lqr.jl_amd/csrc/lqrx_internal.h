@@ -79,14 +79,17 @@ hipError_t dp_value_cost_launch(const DpArgs &a, void *J, hipStream_t s);
 hipError_t batch_transpose(const void *in, void *out, int64_t rows, int64_t cols, int elem_bytes, hipStream_t s);
 bool dp_supported(int dtype, int n, int m, bool tv);
 // Workspace of a canonical-form solve (lqrx_dp_canon.hip writes it, dp_riccati_kernel's VAR_CANON /
-// VAR_MASK variants read it): one int32 flag per trajectory (1: canonical applies), then per
-// trajectory Ã, Q̃, Q̃f, Tᵀ (n² each), R̃, Sᵀ (m² each), column-major.  It reaches those kernels in
+// VAR_MASK / VAR_PREFB variants read it): one int32 flag per trajectory (2: canonical with the
+// pre-feedback, 1: canonical, 0: generic), then per trajectory Ã, Q̃, Q̃f, Tᵀ (n² each), R̃, Sᵀ (m² each),
+// column-major.  A flag-2 trajectory has Q′ in Q̃'s place and behind Sᵀ M′ (m×n, column-major) and C
+// (m×n, as the lanes hold its tiles: tile, lane, register).  It reaches those kernels in
 // DpArgs::M — a plain solve has no cross term, so M is otherwise unread there — and DpArgs, with it
 // every other kernel's argument block, stays as it is.
 template <typename T, int NT, int MT> struct DpCanonWs {
-    static constexpr size_t nn = (size_t)256 * NT * NT, mm = (size_t)256 * MT * MT;
+    static constexpr size_t nn = (size_t)256 * NT * NT, mm = (size_t)256 * MT * MT, nm = (size_t)256 * NT * MT;
     static constexpr size_t oA = 0, oQ = nn, oQf = 2 * nn, oTt = 3 * nn, oR = 4 * nn, oSt = 4 * nn + mm;
-    static constexpr size_t per = 4 * nn + 2 * mm;                     // elements per trajectory
+    static constexpr size_t oMp = 4 * nn + 2 * mm, oC = oMp + nm;
+    static constexpr size_t per = 4 * nn + 2 * mm + 2 * nm;            // elements per trajectory
     static __host__ __device__ size_t flag_bytes(int64_t batch) { return ((size_t)batch * 4 + 255) / 256 * 256; }
     static __host__ __device__ size_t bytes(int64_t batch) { return flag_bytes(batch) + (size_t)batch * per * sizeof(T); }
     static __host__ __device__ int32_t *flags(void *ws) { return (int32_t *)ws; }
@@ -101,13 +104,20 @@ template <typename T, int NT, int MT> struct DpCanonWs {
     }
 };
 // the canonical-form solve of a plain time-invariant fp64 n = 32, m = 16, P_1-only call (lqrx_dp_canon.hip):
-// set-up, VAR_CANON kernel, VAR_MASK kernel.  *ran = false (and nothing launched, hipSuccess) when the
-// pool cannot give the workspace: the caller then takes the generic launch.
+// set-up, VAR_PREFB kernel, VAR_CANON kernel, VAR_MASK kernel.  *ran = false (and nothing launched,
+// hipSuccess) when the pool cannot give the workspace: the caller then takes the generic launch.
 hipError_t dp_canon_launch(const DpArgs &a, hipStream_t s, bool *ran);
+// the VAR_CANON | VAR_PREFB instantiation's launch (lqrx_dp_prefb.hip, a module of its own), on the
+// workspace in a.M, over the whole batch
+hipError_t dp_prefb_launch(const DpArgs &a, hipStream_t s);
 // κ∞(B₁) bound of the canonical form in fp64: a factor 4 under the end of the conditioning sweep of
 // tests/dp_canon_truth.py, which reached cond(B) = 1e14 with the canonical gain still under a tenth
 // of the 1e-10 tolerance
 constexpr double DP_CANON_KAPPA_F64 = 2.5e13;
+// κ∞(B₁) bound of the pre-feedback tier (VAR_PREFB): Q′ carries A₁ᵀR̃A₁, which −GᵀK_v cancels again, and
+// R̃ = SᵀRS grows like κ(B₁)², so digits go in proportion.  A factor 4 under the point of the sweep of
+// tests/dp_canon_pf_truth.py where the modelled gain error first reaches 1e-11
+constexpr double DP_PREFB_KAPPA_F64 = 4.7e2;
 // lane-per-trajectory kernel for n ≤ 4, m ≤ 4 (lqrx_dp_lane.hip)
 hipError_t dp_lane_launch(const DpArgs &a, int kind, hipStream_t s);
 bool dp_lane_supported(int n, int m);

@@ -433,6 +433,84 @@ int lqrx_dp_rollout_host(const lqrx_dp_desc *desc, const void *A, const void *B,
                          const lqrx_dp_scenarios *sc);
 
 /* ------------------------------------------------------------------------------------
+ * Factor once, re-solve many right-hand sides.  P_k, K_k and E_k = R_k + B_kᵀP_{k+1}B_k of a solve
+ * do not depend on q, r, qf, x0: lqrx_dp_factor keeps E_k⁻¹ and g_k = P_{k+1}c_k of one solve, and
+ * lqrx_dp_resolve then solves S right-hand sides (q, r, qf, x0) per problem by vector recursions
+ * alone (no cost matrix is read: the cross term lives in K).  Per problem b and right-hand side j
+ * (trajectory t = b·S + j):
+ *   p_N = qf_t
+ *   p̃   = p_{k+1} + g_k       h_k = r_{t,k} + B_kᵀp̃       d_k = E_k⁻¹h_k
+ *   p_k = q_{t,k} + A_kᵀp̃ − K_kᵀh_k                                              k = N−1 … 1
+ *   x_1 = x0_t,  u_k = −K_k x_k − d_k,  x_{k+1} = A_k x_k + B_k u_k + c_k          k = 1 … N−1
+ * which is what lqrx_dp_solve_cross returns for that right-hand side (d, p, X, U).
+ *
+ * lqrx_dp_factor
+ *   desc        p_mode must be 1 (0: LQRX_ERR_UNSUPPORTED)
+ *   B, R        knot_stride_AB / knot_stride_QR
+ *   c           as in the solve; may be NULL, then Pc must be NULL and is not formed
+ *   P           the p_mode = 1 output of any solve entry: n·n·N·batch, P_N = Qf
+ *   Einv        out, E_k⁻¹: m·m·(N−1)·batch, column-major, exactly symmetric
+ *   Pc          out, P_{k+1}c_k: n·(N−1)·batch (NULL exactly when c is)
+ *   info        optional, batch: 0, or the largest k (1-based) whose E_k is not positive definite —
+ *               the knot the solve's backward sweep would report first.  Einv and Pc of such a
+ *               problem are unspecified (every element is written)
+ * lqrx_dp_resolve
+ *   A, B, c     the dynamics (knot_stride_AB); c may be NULL exactly when fac->Pc is
+ *   fac         K the solve's gains, Einv and Pc from lqrx_dp_factor
+ *   rhs         laid out scenario-major exactly as in lqrx_dp_scenarios (S = 1 is the solve's layout):
+ *                 q_{t,k} at [(t·(N−1) + k−1)·n] with knot_stride_QR = 1, at [t·n] with 0; r likewise with m
+ *                 qf_t, x0_t at [t·n]       d_{t,k} at [(t·(N−1) + k−1)·m]
+ *                 p: p_1 at [t·n] with p_mode 0, p_k at [(t·N + k−1)·n] with p_mode 1 (p_N = qf)
+ *                 x_k at [(t·N + k−1)·n]    u_k at [(t·(N−1) + k−1)·m]
+ *               knot_stride_QR governs only the layout of q and r here.  q, r, qf, x0 may each be
+ *               NULL (zero).  d, p, X, U are each optional, at least one is required; d carries the
+ *               backward pass to the forward one (the entry takes no library scratch), so X or U
+ *               without d is an error on rhs.
+ * Layout 0 only (desc.layout = 1: LQRX_ERR_UNSUPPORTED); 1 ≤ n ≤ 64, 1 ≤ m ≤ 32, both dtypes, both knot
+ * strides; past that LQRX_ERR_UNSUPPORTED (a workgroup kernel up to 512 is a follow-up, as are
+ * layout 1, a c or disturbance per right-hand side, input bounds, s / dV / J per right-hand side,
+ * _host_devices forms, and the use of the re-solve inside lqrx_dp_solve_adjoint).  Error codes follow
+ * the argument position and are decided before the device is touched (lqrx_last_error names the
+ * member, e.g. rhs->S, fac->Einv); batch = 0 returns 0.
+ *   factor:  desc −1, B −2, R −3, P −5, Einv −6, Pc −7 (Pc set without c, or NULL with c)
+ *   resolve: desc −1, A −2, B −3, fac −5 (NULL, K or Einv NULL, Pc / c mismatch), rhs −6 (NULL, S < 1,
+ *            no output, X or U without d)
+ * Guaranteed:
+ *   - a right-hand side's d, p, X, U are the same bits whatever S is, whatever its position j is,
+ *     and whichever outputs are asked for;
+ *   - a NULL q, r, qf or x0 gives the bits of an all-zero array;
+ *   - results of both entries are the same bits from run to run (no atomics);
+ *   - the device entries are one kernel launch each on `stream` and take nothing from the library's
+ *     scratch pool: they can be enqueued or captured like lqrx_dp_rollout.
+ * Additive to ABI 5: detect by symbol.
+ * ------------------------------------------------------------------------------------ */
+typedef struct lqrx_dp_factors {       /* what a re-solve needs beside A, B, c              */
+    const void *K;                     /* the solve's gains, m·n·(N−1)·batch                */
+    const void *Einv;                  /* E_k⁻¹, m·m·(N−1)·batch, column-major, symmetric   */
+    const void *Pc;                    /* P_{k+1}c_k, n·(N−1)·batch; NULL exactly when c is */
+} lqrx_dp_factors;
+
+typedef struct lqrx_dp_rhs {
+    int64_t S;                         /* right-hand sides per problem, >= 1                */
+    const void *q, *r, *qf, *x0;       /* each may be NULL (zero)                           */
+    void *d, *p, *X, *U;               /* out, each optional, at least one                  */
+} lqrx_dp_rhs;
+
+int lqrx_dp_factor(const lqrx_dp_desc *desc, const void *B, const void *R, const void *c,
+                   const void *P, void *Einv, void *Pc, int32_t *info, void *stream);
+
+/* host pointers: H2D, factor, D2H, synchronous */
+int lqrx_dp_factor_host(const lqrx_dp_desc *desc, const void *B, const void *R, const void *c,
+                        const void *P, void *Einv, void *Pc, int32_t *info);
+
+int lqrx_dp_resolve(const lqrx_dp_desc *desc, const void *A, const void *B, const void *c,
+                    const lqrx_dp_factors *fac, const lqrx_dp_rhs *rhs, void *stream);
+
+/* host pointers everywhere (inside fac and rhs too): H2D, re-solve, D2H of the outputs asked for, synchronous */
+int lqrx_dp_resolve_host(const lqrx_dp_desc *desc, const void *A, const void *B, const void *c,
+                         const lqrx_dp_factors *fac, const lqrx_dp_rhs *rhs);
+
+/* ------------------------------------------------------------------------------------
  * KKT path: one inner solve of CholeskySolver._solve!(solver)
  *   /root/reference/src/cholesky_solver.jl:166-182
  * = calculate_shur_factors! (jacobian_blocks.jl:220-286) → cholesky!(chol, shur)

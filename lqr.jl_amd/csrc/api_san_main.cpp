@@ -172,6 +172,87 @@ static void rollout_sweep(double *buf)
     }
 }
 
+// ---- lqrx_dp_factor[_host], lqrx_dp_resolve[_host]: every required pointer NULL in turn, bad S, no output, X
+// without d, the c / Pc mismatch, the unsupported shapes, p_mode and layout — minus the argument's position
+// (factor: B 2, R 3, P 5, Einv 6, Pc 7; resolve: A 2, B 3, fac 5, rhs 6), decided with no device ----
+static int factor_call(bool host, const lqrx_dp_desc *d, const void *B, const void *R, const void *c, const void *P,
+                       void *Einv, void *Pc, int32_t *info)
+{
+    return host ? lqrx_dp_factor_host(d, B, R, c, P, Einv, Pc, info) : lqrx_dp_factor(d, B, R, c, P, Einv, Pc, info, nullptr);
+}
+
+static int resolve_call(bool host, const lqrx_dp_desc *d, const void *A, const void *B, const void *c,
+                        const lqrx_dp_factors *fac, const lqrx_dp_rhs *rhs)
+{
+    return host ? lqrx_dp_resolve_host(d, A, B, c, fac, rhs) : lqrx_dp_resolve(d, A, B, c, fac, rhs, nullptr);
+}
+
+static void resolve_sweep(double *buf, int32_t *info)
+{
+    lqrx_dp_desc d{};
+    d.n = 8; d.m = 4; d.N = 10; d.dtype = LQRX_F64; d.batch = 4; d.p_mode = 1;
+    const lqrx_dp_factors fac{buf, buf, buf};
+    const lqrx_dp_rhs rhs{5, buf, buf, buf, buf, buf, buf, buf, buf};
+    for (int host = 0; host < 2; ++host) {
+        // the factor
+        CHECK(factor_call(host, nullptr, buf, buf, buf, buf, buf, buf, info) == -1);
+        CHECK(factor_call(host, &d, nullptr, buf, buf, buf, buf, buf, info) == -2 && std::strstr(lqrx_last_error(), "B"));
+        CHECK(factor_call(host, &d, buf, nullptr, buf, buf, buf, buf, info) == -3 && std::strstr(lqrx_last_error(), "R"));
+        CHECK(factor_call(host, &d, buf, buf, buf, nullptr, buf, buf, info) == -5 && std::strstr(lqrx_last_error(), "P"));
+        CHECK(factor_call(host, &d, buf, buf, buf, buf, nullptr, buf, info) == -6 && std::strstr(lqrx_last_error(), "Einv"));
+        CHECK(factor_call(host, &d, buf, buf, buf, buf, buf, nullptr, info) == -7 && std::strstr(lqrx_last_error(), "Pc"));
+        CHECK(factor_call(host, &d, buf, buf, nullptr, buf, buf, buf, info) == -7 && std::strstr(lqrx_last_error(), "Pc"));
+        lqrx_dp_desc bad = d;
+        bad.p_mode = 0;
+        CHECK(factor_call(host, &bad, buf, buf, buf, buf, buf, buf, info) == LQRX_ERR_UNSUPPORTED);
+        bad = d; bad.layout = 1;
+        CHECK(factor_call(host, &bad, buf, buf, buf, buf, buf, buf, info) == LQRX_ERR_UNSUPPORTED);
+        bad = d; bad.n = 65;
+        CHECK(factor_call(host, &bad, buf, buf, buf, buf, buf, buf, info) == LQRX_ERR_UNSUPPORTED);
+        bad = d; bad.m = 33;
+        CHECK(factor_call(host, &bad, buf, buf, buf, buf, buf, buf, info) == LQRX_ERR_UNSUPPORTED);
+        bad = d; bad.n = 0;
+        CHECK(factor_call(host, &bad, nullptr, buf, buf, buf, buf, buf, info) == -1);
+        bad = d; bad.batch = 0;                          // empty batch: a no-op whatever the pointers
+        CHECK(factor_call(host, &bad, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == 0);
+        // the re-solve
+        CHECK(resolve_call(host, nullptr, buf, buf, buf, &fac, &rhs) == -1);
+        CHECK(resolve_call(host, &d, nullptr, buf, buf, &fac, &rhs) == -2 && std::strstr(lqrx_last_error(), "A"));
+        CHECK(resolve_call(host, &d, buf, nullptr, buf, &fac, &rhs) == -3 && std::strstr(lqrx_last_error(), "B"));
+        CHECK(resolve_call(host, &d, buf, buf, buf, nullptr, &rhs) == -5 && std::strstr(lqrx_last_error(), "fac"));
+        CHECK(resolve_call(host, &d, buf, buf, buf, &fac, nullptr) == -6 && std::strstr(lqrx_last_error(), "rhs"));
+        lqrx_dp_factors fb = fac; fb.K = nullptr;
+        CHECK(resolve_call(host, &d, buf, buf, buf, &fb, &rhs) == -5 && std::strstr(lqrx_last_error(), "fac->K"));
+        fb = fac; fb.Einv = nullptr;
+        CHECK(resolve_call(host, &d, buf, buf, buf, &fb, &rhs) == -5 && std::strstr(lqrx_last_error(), "fac->Einv"));
+        fb = fac; fb.Pc = nullptr;                       // c without Pc, and Pc without c
+        CHECK(resolve_call(host, &d, buf, buf, buf, &fb, &rhs) == -5 && std::strstr(lqrx_last_error(), "fac->Pc"));
+        CHECK(resolve_call(host, &d, buf, buf, nullptr, &fac, &rhs) == -5 && std::strstr(lqrx_last_error(), "fac->Pc"));
+        lqrx_dp_rhs rb = rhs; rb.S = 0;
+        CHECK(resolve_call(host, &d, buf, buf, buf, &fac, &rb) == -6 && std::strstr(lqrx_last_error(), "rhs->S"));
+        rb = rhs; rb.S = -3;
+        CHECK(resolve_call(host, &d, buf, buf, buf, &fac, &rb) == -6 && std::strstr(lqrx_last_error(), "rhs->S"));
+        rb = rhs; rb.d = rb.p = rb.X = rb.U = nullptr;
+        CHECK(resolve_call(host, &d, buf, buf, buf, &fac, &rb) == -6 && std::strstr(lqrx_last_error(), "rhs->d"));
+        rb = rhs; rb.d = nullptr;                        // X (and U) without d
+        CHECK(resolve_call(host, &d, buf, buf, buf, &fac, &rb) == -6 && std::strstr(lqrx_last_error(), "rhs->X"));
+        rb.X = nullptr;
+        CHECK(resolve_call(host, &d, buf, buf, buf, &fac, &rb) == -6 && std::strstr(lqrx_last_error(), "rhs->U"));
+        rb = rhs; rb.q = rb.r = rb.qf = rb.x0 = nullptr; // optional inputs: the next check answers
+        CHECK(resolve_call(host, &d, nullptr, buf, buf, &fac, &rb) == -2);
+        bad = d; bad.layout = 1;
+        CHECK(resolve_call(host, &bad, buf, buf, buf, &fac, &rhs) == LQRX_ERR_UNSUPPORTED);
+        bad = d; bad.n = 65;
+        CHECK(resolve_call(host, &bad, buf, buf, buf, &fac, &rhs) == LQRX_ERR_UNSUPPORTED);
+        bad = d; bad.m = 33;
+        CHECK(resolve_call(host, &bad, buf, buf, buf, &fac, &rhs) == LQRX_ERR_UNSUPPORTED);
+        bad = d; bad.p_mode = 0;                         // both p modes are served
+        CHECK(resolve_call(host, &bad, nullptr, buf, buf, &fac, &rhs) == -2);
+        bad = d; bad.batch = 0;
+        CHECK(resolve_call(host, &bad, nullptr, nullptr, nullptr, nullptr, nullptr) == 0);
+    }
+}
+
 int main()
 {
     CHECK(lqrx_abi_version() == LQRX_ABI_VERSION);
@@ -217,6 +298,7 @@ int main()
     }
     dp_null_sweep(dummy, info);
     rollout_sweep(dummy);
+    resolve_sweep(dummy, info);
     b = d; b.batch = 0;                                          // empty batch: nothing to do
     CHECK(lqrx_dp_solve(&b, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == 0);
     if (!have_gpu) {                                             // valid call, no device: clean failure

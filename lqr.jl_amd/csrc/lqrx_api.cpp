@@ -781,6 +781,164 @@ int lqrx_dp_rollout_host(const lqrx_dp_desc *d, const void *A, const void *B, co
     return e ? e : st;
 }
 
+} // extern "C"
+
+namespace {
+// Descriptor checks shared by lqrx_dp_factor[_host] and lqrx_dp_resolve[_host]: layout 0, the shapes of
+// the register-tile kernels
+int validate_dp_resolve(const lqrx_dp_desc *d, const char *entry)
+{
+    if (!d) return set_err(-1, "desc is NULL");
+    if (int st = validate_dp(d)) return st;
+    if (d->layout != 0)
+        return set_err(LQRX_ERR_UNSUPPORTED, "%s: desc.layout = 1 is not supported (layout 0 only)", entry);
+    if (!lqrx::dp_resolve_supported(d->n, d->m))
+        return set_err(LQRX_ERR_UNSUPPORTED, "%s: n=%d m=%d is past the kernels' n <= 64, m <= 32", entry, d->n, d->m);
+    return 0;
+}
+
+// The arguments of lqrx_dp_factor[_host] behind desc: B 2, R 3, c 4 (optional), P 5, Einv 6, Pc 7, info 8 (optional)
+int check_factor_args(const void *B, const void *R, const void *c, const void *P, const void *Einv, const void *Pc)
+{
+    if (!B) return set_err(-2, "pointer 2 (B) is NULL");
+    if (!R) return set_err(-3, "pointer 3 (R) is NULL");
+    if (!P) return set_err(-5, "pointer 5 (P) is NULL");
+    if (!Einv) return set_err(-6, "pointer 6 (Einv) is NULL");
+    if (c && !Pc) return set_err(-7, "pointer 7 (Pc) is NULL and c is given");
+    if (!c && Pc) return set_err(-7, "pointer 7 (Pc) is given and c is NULL: there is nothing to form");
+    return 0;
+}
+
+// The arguments of lqrx_dp_resolve[_host] behind desc: A 2, B 3, c 4 (optional), fac 5, rhs 6
+int check_resolve_args(const void *A, const void *B, const void *c, const lqrx_dp_factors *fac, const lqrx_dp_rhs *rhs)
+{
+    if (!A) return set_err(-2, "pointer 2 (A) is NULL");
+    if (!B) return set_err(-3, "pointer 3 (B) is NULL");
+    if (!fac) return set_err(-5, "pointer 5 (fac) is NULL");
+    if (!fac->K) return set_err(-5, "fac->K is NULL");
+    if (!fac->Einv) return set_err(-5, "fac->Einv is NULL");
+    if (c && !fac->Pc) return set_err(-5, "fac->Pc is NULL and c is given");
+    if (!c && fac->Pc) return set_err(-5, "fac->Pc is given and c is NULL");
+    if (!rhs) return set_err(-6, "pointer 6 (rhs) is NULL");
+    if (rhs->S < 1) return set_err(-6, "rhs->S must be >= 1 (got %lld)", (long long)rhs->S);
+    if (!rhs->d && !rhs->p && !rhs->X && !rhs->U)
+        return set_err(-6, "rhs->d, rhs->p, rhs->X and rhs->U are all NULL: nothing to compute");
+    if (!rhs->d && (rhs->X || rhs->U))
+        return set_err(-6, "rhs->d is NULL and rhs->%s is asked for: d carries the backward pass to the forward one",
+                       rhs->X ? "X" : "U");
+    return 0;
+}
+} // namespace
+
+extern "C" {
+
+// E_k⁻¹ and P_{k+1}c_k of a solve, from its p_mode = 1 P (see lqrx.h): one kernel, no scratch
+int lqrx_dp_factor(const lqrx_dp_desc *d, const void *B, const void *R, const void *c, const void *P, void *Einv,
+                   void *Pc, int32_t *info, void *stream)
+{
+    int st = validate_dp_resolve(d, "lqrx_dp_factor");
+    if (st) return st;
+    if (d->p_mode != 1)
+        return set_err(LQRX_ERR_UNSUPPORTED, "lqrx_dp_factor: desc.p_mode must be 1 (P holds every P_k)");
+    if (d->batch == 0) return 0;
+    if ((st = check_factor_args(B, R, c, P, Einv, Pc))) return st;
+    lqrx::DpFactorArgs a{};
+    a.B = B; a.R = R; a.c = c; a.P = P; a.Einv = Einv; a.Pc = Pc; a.info = info;
+    a.n = d->n; a.m = d->m; a.N = d->N; a.dtype = d->dtype;
+    a.tv_AB = (int)d->knot_stride_AB; a.tv_QR = (int)d->knot_stride_QR;
+    a.batch = d->batch;
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = lqrx::dp_factor_launch(a, s);
+    if (e != hipSuccess) return hip_err(e, "factor kernel launch");
+    if (stream == nullptr && (e = hipStreamSynchronize(nullptr)) != hipSuccess) return hip_err(e, "factor kernel");
+    return 0;
+}
+
+int lqrx_dp_factor_host(const lqrx_dp_desc *d, const void *B, const void *R, const void *c, const void *P, void *Einv,
+                        void *Pc, int32_t *info)
+{
+    int st = validate_dp_resolve(d, "lqrx_dp_factor_host");
+    if (st) return st;
+    if (d->p_mode != 1)
+        return set_err(LQRX_ERR_UNSUPPORTED, "lqrx_dp_factor_host: desc.p_mode must be 1 (P holds every P_k)");
+    if (d->batch == 0) return 0;
+    if ((st = check_factor_args(B, R, c, P, Einv, Pc))) return st;
+    const size_t es = dsize(d->dtype), bt = (size_t)d->batch, n = d->n, m = d->m, N = d->N;
+    const size_t kAB = d->knot_stride_AB ? N - 1 : 1, kQR = d->knot_stride_QR ? N - 1 : 1;
+    enum { iB, iR, ic, iP, iE, iPc, iinfo, kBufs };
+    HostBuf hb[kBufs];
+    hb[iB] = host_in(B, n * m * kAB * es * bt);
+    hb[iR] = host_in(R, m * m * kQR * es * bt);
+    hb[ic] = host_in(c, n * kAB * es * bt);
+    hb[iP] = host_in(P, n * n * N * es * bt);
+    hb[iE] = HostBuf{Einv, m * m * (N - 1) * es * bt, H_OUT};
+    hb[iPc] = HostBuf{Pc, n * (N - 1) * es * bt, H_OUT};
+    hb[iinfo] = HostBuf{info, 4 * bt, H_OUT};   // optional: no twin, and NULL to the kernel, when the caller passes none
+    HostStage dev;
+    if ((st = dev.upload(hb, kBufs))) return st;
+    st = lqrx_dp_factor(d, dev[iB], dev[iR], dev[ic], dev[iP], dev[iE], dev[iPc], (int32_t *)dev[iinfo], nullptr);
+    if (st < 0) return st;
+    const int e = dev.download(hb, kBufs);
+    return e ? e : st;
+}
+
+// S right-hand sides per problem on the factors of one solve (see lqrx.h): one kernel, no scratch
+int lqrx_dp_resolve(const lqrx_dp_desc *d, const void *A, const void *B, const void *c, const lqrx_dp_factors *fac,
+                    const lqrx_dp_rhs *rhs, void *stream)
+{
+    int st = validate_dp_resolve(d, "lqrx_dp_resolve");
+    if (st) return st;
+    if (d->batch == 0) return 0;
+    if ((st = check_resolve_args(A, B, c, fac, rhs))) return st;
+    lqrx::DpResolveArgs a{};
+    a.A = A; a.B = B; a.c = c; a.K = fac->K; a.Einv = fac->Einv; a.Pc = fac->Pc;
+    a.q = rhs->q; a.r = rhs->r; a.qf = rhs->qf; a.x0 = rhs->x0;
+    a.d = rhs->d; a.p = rhs->p; a.X = rhs->X; a.U = rhs->U;
+    a.n = d->n; a.m = d->m; a.N = d->N; a.dtype = d->dtype;
+    a.tv_AB = (int)d->knot_stride_AB; a.tv_QR = (int)d->knot_stride_QR; a.p_all = d->p_mode;
+    a.batch = d->batch; a.S = rhs->S;
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = lqrx::dp_resolve_launch(a, s);
+    if (e != hipSuccess) return hip_err(e, "re-solve kernel launch");
+    if (stream == nullptr && (e = hipStreamSynchronize(nullptr)) != hipSuccess) return hip_err(e, "re-solve kernel");
+    return 0;
+}
+
+int lqrx_dp_resolve_host(const lqrx_dp_desc *d, const void *A, const void *B, const void *c, const lqrx_dp_factors *fac,
+                         const lqrx_dp_rhs *rhs)
+{
+    int st = validate_dp_resolve(d, "lqrx_dp_resolve_host");
+    if (st) return st;
+    if (d->batch == 0) return 0;
+    if ((st = check_resolve_args(A, B, c, fac, rhs))) return st;
+    const size_t es = dsize(d->dtype), bt = (size_t)d->batch, n = d->n, m = d->m, N = d->N, S = (size_t)rhs->S;
+    const size_t kAB = d->knot_stride_AB ? N - 1 : 1, kQR = d->knot_stride_QR ? N - 1 : 1, kP = d->p_mode ? N : 1;
+    enum { iA, iB, ic, iK, iE, iPc, iq, ir, iqf, ix0, id, ip, iX, iU, kBufs };
+    HostBuf hb[kBufs];
+    hb[iA] = host_in(A, n * n * kAB * es * bt);
+    hb[iB] = host_in(B, n * m * kAB * es * bt);
+    hb[ic] = host_in(c, n * kAB * es * bt);
+    hb[iK] = host_in(fac->K, m * n * (N - 1) * es * bt);
+    hb[iE] = host_in(fac->Einv, m * m * (N - 1) * es * bt);
+    hb[iPc] = host_in(fac->Pc, n * (N - 1) * es * bt);
+    hb[iq] = host_in(rhs->q, n * kQR * S * es * bt);
+    hb[ir] = host_in(rhs->r, m * kQR * S * es * bt);
+    hb[iqf] = host_in(rhs->qf, n * S * es * bt);
+    hb[ix0] = host_in(rhs->x0, n * S * es * bt);
+    hb[id] = HostBuf{rhs->d, m * (N - 1) * S * es * bt, H_OUT};   // only the outputs asked for have a twin
+    hb[ip] = HostBuf{rhs->p, n * kP * S * es * bt, H_OUT};
+    hb[iX] = HostBuf{rhs->X, n * N * S * es * bt, H_OUT};
+    hb[iU] = HostBuf{rhs->U, m * (N - 1) * S * es * bt, H_OUT};
+    HostStage dev;
+    if ((st = dev.upload(hb, kBufs))) return st;
+    const lqrx_dp_factors dfac{dev[iK], dev[iE], dev[iPc]};
+    const lqrx_dp_rhs drhs{rhs->S, dev[iq], dev[ir], dev[iqf], dev[ix0], dev[id], dev[ip], dev[iX], dev[iU]};
+    st = lqrx_dp_resolve(d, dev[iA], dev[iB], dev[ic], &dfac, &drhs, nullptr);
+    if (st < 0) return st;
+    const int e = dev.download(hb, kBufs);
+    return e ? e : st;
+}
+
 // Gradients of a loss ℓ(X, U) through the solve: one more cross solve with ∂ℓ/∂X, ∂ℓ/∂U as the
 // linear cost terms (x0' = 0, c' = 0), its costates, and the rank-2 assembly (see lqrx.h)
 int lqrx_dp_solve_adjoint(const lqrx_dp_desc *d, const void *A, const void *B, const void *Q, const void *R,

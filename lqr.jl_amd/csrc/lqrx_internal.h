@@ -173,6 +173,36 @@ struct DpScenArgs {
 };
 hipError_t dp_scen_launch(const DpScenArgs &a, hipStream_t s);
 
+// ---- factor once, re-solve S right-hand sides per problem (lqrx_dp_resolve.hip), layout 0, n ≤ 64, m ≤ 32 ----
+// Factor: E_k⁻¹ (m·m per knot, symmetric) and, with c, Pc_k = P_{k+1}c_k (n per knot) from the p_all P
+// of a solve; info (may be null) the largest knot whose E is not positive definite.  B, c follow
+// tv_AB, R follows tv_QR.  One kernel, no scratch.
+struct DpFactorArgs {
+    const void *B, *R, *c, *P;   // c null exactly when Pc is
+    void *Einv, *Pc;
+    int32_t *info;
+    int n, m, N;
+    int dtype; // 0 f64, 1 f32
+    int tv_AB, tv_QR;
+    int64_t batch;
+};
+hipError_t dp_factor_launch(const DpFactorArgs &a, hipStream_t s);
+// Re-solve: trajectory t = b·S + j: p_N = qf_t, p̃ = p_{k+1} + Pc_k, h = r_{t,k} + B_kᵀp̃, d_k = E_k⁻¹h,
+// p_k = q_{t,k} + A_kᵀp̃ − K_kᵀh; x_1 = x0_t, u_k = −K_k x_k − d_k, x_{k+1} = A_k x_k + B_k u_k + c_k.
+// A, B, c follow tv_AB; tv_QR is the knot stride of q and r alone.  q, r, qf, x0 may be null (zero);
+// d, p (n, or n·N with p_all), X, U may be null (not formed), X or U needs d.  One kernel, no scratch.
+struct DpResolveArgs {
+    const void *A, *B, *c, *K, *Einv, *Pc;
+    const void *q, *r, *qf, *x0;
+    void *d, *p, *X, *U;
+    int n, m, N;
+    int dtype; // 0 f64, 1 f32
+    int tv_AB, tv_QR, p_all;
+    int64_t batch, S;
+};
+hipError_t dp_resolve_launch(const DpResolveArgs &a, hipStream_t s);
+bool dp_resolve_supported(int n, int m);
+
 struct KktArgs {
     const double *Y, *y, *H, *g; // device, packed per trajectory
     double *dz, *lam;

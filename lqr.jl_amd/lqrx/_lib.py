@@ -59,6 +59,18 @@ class DpScenarios(C.Structure):
     _fields_ = [("S", C.c_int64)] + [(k, C.c_void_p) for k in ("x0", "alpha", "w", "u_lo", "u_hi", "X", "U", "J")]
 
 
+class DpFactors(C.Structure):
+    """Mirror of ``lqrx_dp_factors`` (what lqrx_dp_resolve needs beside A, B, c: K, Einv; Pc exactly with c)."""
+
+    _fields_ = [(k, C.c_void_p) for k in ("K", "Einv", "Pc")]
+
+
+class DpRhs(C.Structure):
+    """Mirror of ``lqrx_dp_rhs`` (S; q, r, qf, x0 optional in; d, p, X, U optional out, X or U needs d)."""
+
+    _fields_ = [("S", C.c_int64)] + [(k, C.c_void_p) for k in ("q", "r", "qf", "x0", "d", "p", "X", "U")]
+
+
 class KktDesc(C.Structure):
     """Mirror of ``lqrx_kkt_desc``."""
 
@@ -140,6 +152,10 @@ _SIGS = {
     "lqrx_dp_costates_host": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 13),
     "lqrx_dp_rollout": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 5 + [C.POINTER(DpCost), C.POINTER(DpScenarios), _VP]),
     "lqrx_dp_rollout_host": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 5 + [C.POINTER(DpCost), C.POINTER(DpScenarios)]),
+    "lqrx_dp_factor": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 7 + [_VP]),
+    "lqrx_dp_factor_host": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 7),
+    "lqrx_dp_resolve": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 3 + [C.POINTER(DpFactors), C.POINTER(DpRhs), _VP]),
+    "lqrx_dp_resolve_host": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 3 + [C.POINTER(DpFactors), C.POINTER(DpRhs)]),
     "lqrx_dp_solve_adjoint": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 9 + [C.POINTER(DpGrad)]
                               + [_VP, _VP]),
     "lqrx_kkt_solve_host_devices": (C.c_int, [C.POINTER(KktDesc)] + [_VP] * 7 + [_VP, C.c_int32]),

@@ -30,7 +30,8 @@ from . import _lib
 
 __all__ = ["LQRProblem", "LQRSolution", "DPSolver", "solve", "solve_batch", "LQRBatch",
            "random_batch", "to_abi", "from_abi", "dp_solve_device", "compute_gain", "compute_ctg",
-           "compute_ctg_batch", "rollout_batch", "dp_rollout_device"]
+           "compute_ctg_batch", "rollout_batch", "dp_rollout_device", "factor_batch", "resolve_batch",
+           "dp_factor_device", "dp_resolve_device"]
 
 
 def to_abi(a: np.ndarray) -> np.ndarray:
@@ -560,6 +561,181 @@ def dp_rollout_device(t: dict, N: int, K, d, sc: dict, stream: int | None = None
     rc = _lib.check(lib.lqrx_dp_rollout(C.byref(desc), vp(t["A"]), vp(t["B"]), vp(t.get("c")), vp(K), vp(d),
                                         C.byref(ct) if "J" in outputs else None, C.byref(scn),
                                         C.c_void_p(stream) if stream else None))
+    res = {k: out[k] for k in outputs}
+    res["rc"] = rc
+    return res
+
+
+_RESOLVE_OUT = ("d", "p", "X", "U")
+
+
+def _resolve_outputs(who: str, outputs) -> tuple:
+    outputs = tuple(outputs)
+    if not outputs or any(k not in _RESOLVE_OUT for k in outputs):
+        raise ValueError(f"{who}: outputs must name at least one of {_RESOLVE_OUT} (got {outputs})")
+    if "d" not in outputs and ("X" in outputs or "U" in outputs):
+        raise ValueError(f"{who}: X and U need d among the outputs (d carries the backward pass to the forward one)")
+    return outputs
+
+
+def factor_batch(b: LQRBatch, P, dtype: int = _lib.F64) -> dict:
+    """E_k⁻¹ and P_{k+1}c_k of a solved batch, through lqrx_dp_factor_host: what resolve_batch needs
+    beside the solve's K.  b gives B, R (and c); P (batch, N, n, n) is every P_k of the solve
+    (solve_batch(..., all_P=True)).  Returns Einv (batch, N−1, m, m), Pc (batch, N−1, n) or None
+    without b.c, info (batch: 0, or the largest knot whose E is not positive definite) and rc."""
+    n, m, N = b.size()
+    bt = b.batch
+    tvAB, tvQR = b.time_varying()
+    npdt = np.float64 if dtype == _lib.F64 else np.float32
+    P = np.asarray(P, dtype=npdt)
+    if P.shape != (bt, N, n, n):
+        raise ValueError(f"factor_batch: P is (batch, N, n, n) = {(bt, N, n, n)}, every P_k of the solve (got {P.shape})")
+    kab = N - 1 if tvAB else 1
+    c = None if b.c is None else np.ascontiguousarray(np.asarray(b.c, dtype=npdt)).reshape(-1)
+    if c is not None and c.size != bt * kab * n:
+        raise ValueError(f"factor_batch: c has {c.size} elements, expected {bt * kab * n}")
+    mat = lambda a: to_abi(np.asarray(a, dtype=npdt)).reshape(-1)
+    Bf, Rf, Pf = mat(b.B), mat(b.R), mat(P)
+    Einv = np.zeros(bt * (N - 1) * m * m, npdt)
+    Pc = None if c is None else np.zeros(bt * (N - 1) * n, npdt)
+    info = np.zeros(bt, np.int32)
+    p = lambda a: None if a is None else a.ctypes.data
+    desc = _lib.DpDesc(n, m, N, dtype, bt, 0, 1, tvAB, tvQR)
+    rc = _lib.check(_lib.load().lqrx_dp_factor_host(C.byref(desc), p(Bf), p(Rf), p(c), p(Pf), p(Einv), p(Pc), p(info)))
+    return dict(Einv=from_abi(Einv, (bt, N - 1, m, m)), Pc=None if Pc is None else Pc.reshape(bt, N - 1, n),
+                info=info, rc=rc)
+
+
+def resolve_batch(b: LQRBatch, K, fac: dict, x0=None, q=None, r=None, qf=None, all_p: bool = False,
+                  dtype: int = _lib.F64, outputs=_RESOLVE_OUT) -> dict:
+    """S new right-hand sides per problem on the factors of one solve, through lqrx_dp_resolve_host.
+
+    b gives A, B (and c); K (batch, N−1, m, n) is the solve's gain, fac = dict(Einv=, Pc=) what
+    factor_batch returned (Pc None exactly when b.c is).  x0, qf (batch, S, n); q (batch, S, n) or
+    (batch, S, N−1, n); r (batch, S, m) or (batch, S, N−1, m), with a knot axis on both or neither; each
+    may be None (zero), at least one sets S.  Returns those of d (batch, S, N−1, m), p (batch, S, n),
+    or (batch, S, N, n) with all_p), X (batch, S, N, n), U (batch, S, N−1, m) that `outputs` names, and rc."""
+    n, m, N = b.size()
+    bt = b.batch
+    tvAB, _ = b.time_varying()
+    npdt = np.float64 if dtype == _lib.F64 else np.float32
+    outputs = _resolve_outputs("resolve_batch", outputs)
+    given = {k: np.asarray(v, dtype=npdt) for k, v in dict(x0=x0, q=q, r=r, qf=qf).items() if v is not None}
+    if not given:
+        raise ValueError("resolve_batch: at least one of x0, q, r, qf must be given (it sets S)")
+    first = next(iter(given.values()))
+    S = first.shape[1] if first.ndim >= 2 else 0
+    if S < 1:
+        raise ValueError("resolve_batch: right-hand sides are (batch, S, ...) with S >= 1")
+    for k in ("x0", "qf"):
+        if k in given and given[k].shape != (bt, S, n):
+            raise ValueError(f"resolve_batch: {k} is (batch, S, n) = {(bt, S, n)} (got {given[k].shape})")
+    knot = {k: given[k].ndim == 4 for k in ("q", "r") if k in given}
+    if len(set(knot.values())) > 1:
+        raise ValueError("resolve_batch: q and r carry a knot axis (batch, S, N-1, ·) both or neither")
+    tvQR = int(any(knot.values()))
+    for k, w in (("q", n), ("r", m)):
+        want = (bt, S, N - 1, w) if tvQR else (bt, S, w)
+        if k in given and given[k].shape != want:
+            raise ValueError(f"resolve_batch: {k} is {want} (got {given[k].shape})")
+    flat = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a, dtype=npdt)).reshape(-1)
+    mat = lambda a: None if a is None else to_abi(np.asarray(a, dtype=npdt)).reshape(-1)
+
+    def sized(name, a, size):
+        if a is not None and a.size != size:
+            raise ValueError(f"resolve_batch: {name} has {a.size} elements, expected {size}")
+        return a
+
+    kab = N - 1 if tvAB else 1
+    if fac.get("Einv") is None:
+        raise ValueError("resolve_batch: fac needs Einv (factor_batch's)")
+    if (fac.get("Pc") is None) != (b.c is None):
+        raise ValueError("resolve_batch: fac['Pc'] is given exactly when the batch has c")
+    ins = dict(A=mat(b.A), B=mat(b.B), c=sized("c", flat(b.c), bt * kab * n),
+               K=sized("K", mat(K), bt * (N - 1) * m * n), Einv=sized("Einv", mat(fac["Einv"]), bt * (N - 1) * m * m),
+               Pc=sized("Pc", flat(fac.get("Pc")), bt * (N - 1) * n))
+    rh = {k: flat(given.get(k)) for k in ("q", "r", "qf", "x0")}
+    kp = N if all_p else 1
+    sizes = dict(d=bt * S * (N - 1) * m, p=bt * S * kp * n, X=bt * S * N * n, U=bt * S * (N - 1) * m)
+    out = {k: np.zeros(sizes[k], npdt) for k in outputs}
+    p = lambda a: None if a is None else a.ctypes.data
+    fc = _lib.DpFactors(p(ins["K"]), p(ins["Einv"]), p(ins["Pc"]))
+    rs = _lib.DpRhs(S, *[p(rh[k]) for k in ("q", "r", "qf", "x0")], *[p(out.get(k)) for k in _RESOLVE_OUT])
+    desc = _lib.DpDesc(n, m, N, dtype, bt, 0, int(all_p), tvAB, tvQR)
+    rc = _lib.check(_lib.load().lqrx_dp_resolve_host(C.byref(desc), p(ins["A"]), p(ins["B"]), p(ins["c"]),
+                                                     C.byref(fc), C.byref(rs)))
+    shapes = dict(d=(bt, S, N - 1, m), p=(bt, S, N, n) if all_p else (bt, S, n), X=(bt, S, N, n), U=(bt, S, N - 1, m))
+    res = {k: out[k].reshape(shapes[k]) for k in outputs}
+    res["rc"] = rc
+    return res
+
+
+def dp_factor_device(t: dict, N: int, P, out: dict | None = None, stream: int | None = None) -> dict:
+    """Device-pointer entry point of lqrx_dp_factor on torch tensors already in ABI layout (flat,
+    layout 0), in the manner of dp_rollout_device.
+
+    t: tensors B, R and optionally c, ints n, m, batch and optional tv_AB / tv_QR.  P: every P_k of a
+    solve (dp_solve_device(..., p_mode=1)["P"], n·n·N·batch).  `out` may hold preallocated Einv
+    (m·m·(N−1)·batch), Pc (n·(N−1)·batch) and info (int32, batch).  Returns dict(Einv, Pc (None without
+    t["c"]), info, rc).  `stream` is a raw hipStream_t; None = the null stream, synchronous.  The call
+    allocates nothing inside the library."""
+    import torch
+
+    n, m, bt = t["n"], t["m"], t["batch"]
+    tdt = t["B"].dtype
+    dtype = _lib.F64 if tdt == torch.float64 else _lib.F32
+    dev = t["B"].device
+    c = t.get("c")
+    out = {} if out is None else out
+    if out.get("Einv") is None:
+        out["Einv"] = torch.empty(bt * (N - 1) * m * m, dtype=tdt, device=dev)
+    if c is None:
+        out["Pc"] = None
+    elif out.get("Pc") is None:
+        out["Pc"] = torch.empty(bt * (N - 1) * n, dtype=tdt, device=dev)
+    if out.get("info") is None:
+        out["info"] = torch.empty(bt, dtype=torch.int32, device=dev)
+    desc = _lib.DpDesc(n, m, N, dtype, bt, 0, 1, int(t.get("tv_AB", 0)), int(t.get("tv_QR", 0)))
+    vp = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+    rc = _lib.check(_lib.load().lqrx_dp_factor(C.byref(desc), vp(t["B"]), vp(t["R"]), vp(c), vp(P), vp(out["Einv"]),
+                                               vp(out["Pc"]), vp(out["info"]), C.c_void_p(stream) if stream else None))
+    return dict(Einv=out["Einv"], Pc=out["Pc"], info=out["info"], rc=rc)
+
+
+def dp_resolve_device(t: dict, N: int, fac: dict, rhs: dict, stream: int | None = None, out: dict | None = None) -> dict:
+    """Device-pointer entry point of lqrx_dp_resolve on torch tensors already in ABI layout (flat,
+    layout 0), in the manner of dp_rollout_device.
+
+    t: tensors A, B and optionally c, ints n, m, batch and optional tv_AB; t["tv_QR"] is not read.
+    fac = dict(K=, Einv=, Pc=): the solve's gains and dp_factor_device's tensors (Pc None exactly when
+    t has no c).  rhs = dict(S=, q=, r=, qf=, x0=, outputs=("d", "p", "X", "U")): the right-hand sides,
+    trajectory t = b·S + j, each tensor optional (zero); "tv_QR" (default 0) says whether q and r carry
+    a knot axis (n·(N−1) resp. m·(N−1) per trajectory), "p_mode" (default 0) whether p holds every p_k
+    (n·N per trajectory).  `out` may hold preallocated d, p, X, U.  Returns the dict of output tensors
+    and rc.  `stream` is a raw hipStream_t; None = the null stream, synchronous.  The call allocates
+    nothing inside the library."""
+    import torch
+
+    outputs = _resolve_outputs("dp_resolve_device", rhs.get("outputs", _RESOLVE_OUT))
+    n, m, bt = t["n"], t["m"], t["batch"]
+    tdt = t["A"].dtype
+    dtype = _lib.F64 if tdt == torch.float64 else _lib.F32
+    dev = t["A"].device
+    S = int(rhs["S"])
+    p_mode = int(rhs.get("p_mode", 0))
+    sizes = dict(d=bt * S * (N - 1) * m, p=bt * S * (N if p_mode else 1) * n, X=bt * S * N * n, U=bt * S * (N - 1) * m)
+    out = {} if out is None else out
+    for k in outputs:
+        if out.get(k) is None:
+            out[k] = torch.empty(sizes[k], dtype=tdt, device=dev)
+    p = lambda x: None if x is None else x.data_ptr()
+    fc = _lib.DpFactors(p(fac.get("K")), p(fac.get("Einv")), p(fac.get("Pc")))
+    rs = _lib.DpRhs(S, *[p(rhs.get(k)) for k in ("q", "r", "qf", "x0")],
+                    *[p(out[k]) if k in outputs else None for k in _RESOLVE_OUT])
+    desc = _lib.DpDesc(n, m, N, dtype, bt, 0, p_mode, int(t.get("tv_AB", 0)), int(rhs.get("tv_QR", 0)))
+    vp = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+    rc = _lib.check(_lib.load().lqrx_dp_resolve(C.byref(desc), vp(t["A"]), vp(t["B"]), vp(t.get("c")), C.byref(fc),
+                                                C.byref(rs), C.c_void_p(stream) if stream else None))
     res = {k: out[k] for k in outputs}
     res["rc"] = rc
     return res

@@ -468,8 +468,9 @@ int lqrx_dp_rollout_host(const lqrx_dp_desc *desc, const void *A, const void *B,
  *               without d is an error on rhs.
  * Layout 0 only (desc.layout = 1: LQRX_ERR_UNSUPPORTED); 1 ≤ n ≤ 64, 1 ≤ m ≤ 32, both dtypes, both knot
  * strides; past that LQRX_ERR_UNSUPPORTED (a workgroup kernel up to 512 is a follow-up, as are
- * layout 1, a c or disturbance per right-hand side, input bounds, s / dV / J per right-hand side,
- * _host_devices forms, and the use of the re-solve inside lqrx_dp_solve_adjoint).  Error codes follow
+ * layout 1, a c or disturbance per right-hand side, s / dV / J per right-hand side, _host_devices
+ * forms, and the use of the re-solve inside lqrx_dp_solve_adjoint; input bounds are served by
+ * lqrx_dp_resolve_box below).  Error codes follow
  * the argument position and are decided before the device is touched (lqrx_last_error names the
  * member, e.g. rhs->S, fac->Einv); batch = 0 returns 0.
  *   factor:  desc −1, B −2, R −3, P −5, Einv −6, Pc −7 (Pc set without c, or NULL with c)
@@ -509,6 +510,79 @@ int lqrx_dp_resolve(const lqrx_dp_desc *desc, const void *A, const void *B, cons
 /* host pointers everywhere (inside fac and rhs too): H2D, re-solve, D2H of the outputs asked for, synchronous */
 int lqrx_dp_resolve_host(const lqrx_dp_desc *desc, const void *A, const void *B, const void *c,
                          const lqrx_dp_factors *fac, const lqrx_dp_rhs *rhs);
+
+/* ------------------------------------------------------------------------------------
+ * Input bounds u_lo ≤ u_k ≤ u_hi by ADMM on the re-solve factors.  For S instances per problem,
+ *   min Σ_k (½xᵀQx + uᵀMx + ½uᵀRu + qᵀx + rᵀu) + ½x_NᵀQf x_N + qfᵀx_N
+ *   subject to x⁺ = Ax + Bu + c and u_lo_b ≤ u_k ≤ u_hi_b,
+ * on the factors (K, E⁻¹, Pc) of ONE solve made with R + ρI in the place of R (lqrx_dp_solve_cross,
+ * p_mode = 1, then lqrx_dp_factor, both on R + ρI).  Per problem b and instance j (trajectory
+ * t = b·S + j, scenario-major as in lqrx_dp_rhs), with z_{t,k}, w_{t,k} ∈ ℝᵐ for k = 1 … N−1, the
+ * iteration i = 1 … max_iter is
+ *   r̂_k  = r_{t,k} − ρ(z_k − w_k)
+ *   (d, X, U) = the recursion of lqrx_dp_resolve on (q_t, r̂, qf_t, x0_t)
+ *   û_k  = αu_k + (1 − α)z_k                                  α = relax
+ *   z⁺_k = min(max(û_k + w_k, u_lo_b), u_hi_b)
+ *   w⁺_k = w_k + û_k − z⁺_k
+ *   r_prim = max_k ‖u_k − z⁺_k‖∞      r_dual = ρ·max_k ‖z⁺_k − z_k‖∞
+ * and the instance stops after the first iteration with r_prim ≤ eps_prim and r_dual ≤ eps_dual.
+ * At the fixed point z = u is the constrained optimum and y = ρ·w the multiplier of the bounds
+ * (positive at an active upper bound, negative at a lower one).  Z and W are in/out: zeros are a
+ * cold start, the values of the previous MPC step a warm start.  d, X, U are those of the
+ * instance's last iteration (U is u, which meets the bounds to r_prim; Z meets them exactly).
+ *
+ *   rhs         as in lqrx_dp_resolve; d is required (it carries the backward pass to the forward
+ *               one), X and U are optional, p must be NULL
+ *   box->rho    > 0 and finite: the ρ the factors were made with
+ *   box->relax  in [1, 2); 1 is plain ADMM
+ *   box->eps_*  >= 0, absolute.  An eps of 0 never stops early: the instance runs max_iter
+ *               iterations (early stopping needs both eps > 0).  A NaN residual never stops.
+ *   box->max_iter  1 … 10000
+ *   box->u_lo, u_hi  m·batch each, one bound per problem and input, or NULL (no bound on that
+ *               side); ±inf allowed
+ *   box->Z, W   in/out, m·(N−1)·S·batch each, laid out as rhs->U; required
+ *   box->iters  out, optional, S·batch: the iterations the instance ran
+ *   box->res    out, optional, 2·S·batch: r_prim, r_dual of its last iteration at [2t], [2t + 1]
+ * The support is that of lqrx_dp_resolve: layout 0, 1 ≤ n ≤ 64, 1 ≤ m ≤ 32, both dtypes, both knot
+ * strides, any S ≥ 1; anything else LQRX_ERR_UNSUPPORTED.  Error codes follow the argument position
+ * and are decided before the device is touched (lqrx_last_error names the member); batch = 0
+ * returns 0:
+ *   desc −1, A −2, B −3, fac −5 (as in the re-solve), rhs −6 (NULL, S < 1, d NULL, p given),
+ *   box −7 (NULL, rho, relax, eps_prim, eps_dual, max_iter out of range, Z or W NULL)
+ * Guaranteed:
+ *   - an instance's Z, W, d, X, U, iters and res are the same bits whatever S is, whatever its
+ *     position j is, whichever optional outputs are asked for, and whatever the other instances do
+ *     (an instance that has stopped stores nothing more);
+ *   - NULL u_lo / u_hi give the bits of −inf / +inf arrays, NULL q, r, qf, x0 those of zeros;
+ *   - the same bits from run to run (no atomics);
+ *   - continuation is exact: with eps = 0, a run of a iterations followed by a run of b iterations
+ *     on the returned Z, W gives the bits of one run of a + b;
+ *   - the iteration loop is counted and bounded by max_iter;
+ *   - the device entry is one kernel launch on `stream` and takes nothing from the library's
+ *     scratch pool: it can be enqueued or captured like lqrx_dp_resolve.
+ * Follow-ups: state or mixed constraints, a ρ per problem or an adaptive ρ (a re-factor), shapes
+ * past n = 64 or m = 32, layout 1, a _host_devices form, a gradient through the constrained solve.
+ * Additive to ABI 5: detect by symbol.
+ * ------------------------------------------------------------------------------------ */
+typedef struct lqrx_dp_box {
+    double rho;                  /* > 0; the factors must come from a solve with R + rho·I           */
+    double relax;                /* in [1, 2); 1 = plain ADMM                                        */
+    double eps_prim, eps_dual;   /* >= 0, absolute; 0 never stops early                              */
+    int32_t max_iter;            /* 1 … 10000                                                        */
+    const void *u_lo, *u_hi;     /* m·batch each, or NULL (no bound on that side); ±inf allowed      */
+    void *Z, *W;                 /* in/out, m·(N−1)·S·batch each, laid out as rhs->U; required       */
+    int32_t *iters;              /* out, optional, S·batch: iterations this instance ran             */
+    void *res;                   /* out, optional, 2·S·batch: r_prim, r_dual of its last iteration   */
+} lqrx_dp_box;
+
+int lqrx_dp_resolve_box(const lqrx_dp_desc *desc, const void *A, const void *B, const void *c,
+                        const lqrx_dp_factors *fac, const lqrx_dp_rhs *rhs, const lqrx_dp_box *box,
+                        void *stream);
+
+/* host pointers everywhere (inside fac, rhs and box too): H2D (Z and W included), the iteration, D2H of Z, W
+   and the outputs asked for, synchronous */
+int lqrx_dp_resolve_box_host(const lqrx_dp_desc *desc, const void *A, const void *B, const void *c,
+                             const lqrx_dp_factors *fac, const lqrx_dp_rhs *rhs, const lqrx_dp_box *box);
 
 /* ------------------------------------------------------------------------------------
  * KKT path: one inner solve of CholeskySolver._solve!(solver)

@@ -253,6 +253,85 @@ static void resolve_sweep(double *buf, int32_t *info)
     }
 }
 
+// ---- lqrx_dp_resolve_box[_host]: every required pointer NULL in turn, the members of rhs and box the entry
+// refuses, the ends of the ranges, the unsupported shapes — minus the argument's position (A 2, B 3, fac 5,
+// rhs 6, box 7), decided with no device ----
+static int box_call(bool host, const lqrx_dp_desc *d, const void *A, const void *B, const void *c,
+                    const lqrx_dp_factors *fac, const lqrx_dp_rhs *rhs, const lqrx_dp_box *box)
+{
+    return host ? lqrx_dp_resolve_box_host(d, A, B, c, fac, rhs, box) : lqrx_dp_resolve_box(d, A, B, c, fac, rhs, box, nullptr);
+}
+
+static void box_sweep(double *buf, int32_t *info)
+{
+    lqrx_dp_desc d{};
+    d.n = 8; d.m = 4; d.N = 10; d.dtype = LQRX_F64; d.batch = 4;
+    const lqrx_dp_factors fac{buf, buf, buf};
+    const lqrx_dp_rhs rhs{5, buf, buf, buf, buf, buf, nullptr, buf, buf};
+    const lqrx_dp_box box{1.0, 1.6, 1e-6, 1e-6, 100, buf, buf, buf, buf, info, buf};
+    const double nan = std::nan(""), inf = HUGE_VAL;
+    for (int host = 0; host < 2; ++host) {
+        CHECK(box_call(host, nullptr, buf, buf, buf, &fac, &rhs, &box) == -1);
+        CHECK(box_call(host, &d, nullptr, buf, buf, &fac, &rhs, &box) == -2 && std::strstr(lqrx_last_error(), "A"));
+        CHECK(box_call(host, &d, buf, nullptr, buf, &fac, &rhs, &box) == -3 && std::strstr(lqrx_last_error(), "B"));
+        CHECK(box_call(host, &d, buf, buf, buf, nullptr, &rhs, &box) == -5 && std::strstr(lqrx_last_error(), "fac"));
+        CHECK(box_call(host, &d, buf, buf, buf, &fac, nullptr, &box) == -6 && std::strstr(lqrx_last_error(), "rhs"));
+        CHECK(box_call(host, &d, buf, buf, buf, &fac, &rhs, nullptr) == -7 && std::strstr(lqrx_last_error(), "box"));
+        lqrx_dp_factors fb = fac; fb.K = nullptr;
+        CHECK(box_call(host, &d, buf, buf, buf, &fb, &rhs, &box) == -5 && std::strstr(lqrx_last_error(), "fac->K"));
+        fb = fac; fb.Einv = nullptr;
+        CHECK(box_call(host, &d, buf, buf, buf, &fb, &rhs, &box) == -5 && std::strstr(lqrx_last_error(), "fac->Einv"));
+        fb = fac; fb.Pc = nullptr;                       // c without Pc, and Pc without c
+        CHECK(box_call(host, &d, buf, buf, buf, &fb, &rhs, &box) == -5 && std::strstr(lqrx_last_error(), "fac->Pc"));
+        CHECK(box_call(host, &d, buf, buf, nullptr, &fac, &rhs, &box) == -5 && std::strstr(lqrx_last_error(), "fac->Pc"));
+        lqrx_dp_rhs rb = rhs; rb.S = 0;
+        CHECK(box_call(host, &d, buf, buf, buf, &fac, &rb, &box) == -6 && std::strstr(lqrx_last_error(), "rhs->S"));
+        rb = rhs; rb.d = nullptr;
+        CHECK(box_call(host, &d, buf, buf, buf, &fac, &rb, &box) == -6 && std::strstr(lqrx_last_error(), "rhs->d"));
+        rb = rhs; rb.p = buf;
+        CHECK(box_call(host, &d, buf, buf, buf, &fac, &rb, &box) == -6 && std::strstr(lqrx_last_error(), "rhs->p"));
+        const struct { double lqrx_dp_box::*field; double bad; const char *name; } reals[] = {
+            {&lqrx_dp_box::rho, 0.0, "box->rho"}, {&lqrx_dp_box::rho, -1.0, "box->rho"}, {&lqrx_dp_box::rho, nan, "box->rho"},
+            {&lqrx_dp_box::rho, inf, "box->rho"}, {&lqrx_dp_box::relax, 0.99, "box->relax"}, {&lqrx_dp_box::relax, 2.0, "box->relax"},
+            {&lqrx_dp_box::relax, nan, "box->relax"}, {&lqrx_dp_box::eps_prim, -1e-9, "box->eps_prim"},
+            {&lqrx_dp_box::eps_prim, nan, "box->eps_prim"}, {&lqrx_dp_box::eps_dual, -1.0, "box->eps_dual"},
+            {&lqrx_dp_box::eps_dual, nan, "box->eps_dual"}};
+        for (const auto &e : reals) {
+            lqrx_dp_box bb = box;
+            bb.*(e.field) = e.bad;
+            CHECK(box_call(host, &d, buf, buf, buf, &fac, &rhs, &bb) == -7 && std::strstr(lqrx_last_error(), e.name));
+        }
+        lqrx_dp_box bb = box; bb.max_iter = 0;
+        CHECK(box_call(host, &d, buf, buf, buf, &fac, &rhs, &bb) == -7 && std::strstr(lqrx_last_error(), "box->max_iter"));
+        bb = box; bb.max_iter = 10001;
+        CHECK(box_call(host, &d, buf, buf, buf, &fac, &rhs, &bb) == -7 && std::strstr(lqrx_last_error(), "box->max_iter"));
+        bb = box; bb.Z = nullptr;
+        CHECK(box_call(host, &d, buf, buf, buf, &fac, &rhs, &bb) == -7 && std::strstr(lqrx_last_error(), "box->Z"));
+        bb = box; bb.W = nullptr;
+        CHECK(box_call(host, &d, buf, buf, buf, &fac, &rhs, &bb) == -7 && std::strstr(lqrx_last_error(), "box->W"));
+        // optional members and the ends of the ranges: the next check answers
+        bb = box; bb.u_lo = bb.u_hi = nullptr; bb.iters = nullptr; bb.res = nullptr;
+        bb.relax = 1.0; bb.eps_prim = bb.eps_dual = 0.0; bb.max_iter = 10000;
+        rb = rhs; rb.q = rb.r = rb.qf = rb.x0 = nullptr; rb.X = rb.U = nullptr;
+        CHECK(box_call(host, &d, nullptr, buf, buf, &fac, &rb, &bb) == -2);
+        bb = box; bb.max_iter = 1; bb.eps_prim = inf;
+        CHECK(box_call(host, &d, nullptr, buf, buf, &fac, &rhs, &bb) == -2);
+        lqrx_dp_desc bad = d;
+        bad.layout = 1;
+        CHECK(box_call(host, &bad, buf, buf, buf, &fac, &rhs, &box) == LQRX_ERR_UNSUPPORTED);
+        bad = d; bad.n = 65;
+        CHECK(box_call(host, &bad, buf, buf, buf, &fac, &rhs, &box) == LQRX_ERR_UNSUPPORTED);
+        bad = d; bad.m = 33;
+        CHECK(box_call(host, &bad, buf, buf, buf, &fac, &rhs, &box) == LQRX_ERR_UNSUPPORTED);
+        bad = d; bad.n = 0;
+        CHECK(box_call(host, &bad, nullptr, buf, buf, &fac, &rhs, &box) == -1);
+        bad = d; bad.p_mode = 1;                         // p_mode is not read: the next check answers
+        CHECK(box_call(host, &bad, nullptr, buf, buf, &fac, &rhs, &box) == -2);
+        bad = d; bad.batch = 0;
+        CHECK(box_call(host, &bad, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == 0);
+    }
+}
+
 int main()
 {
     CHECK(lqrx_abi_version() == LQRX_ABI_VERSION);
@@ -299,6 +378,7 @@ int main()
     dp_null_sweep(dummy, info);
     rollout_sweep(dummy);
     resolve_sweep(dummy, info);
+    box_sweep(dummy, info);
     b = d; b.batch = 0;                                          // empty batch: nothing to do
     CHECK(lqrx_dp_solve(&b, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == 0);
     if (!have_gpu) {                                             // valid call, no device: clean failure

@@ -294,7 +294,8 @@ hipError_t dp_launch_soa_staged(const lqrx_dp_desc *d, const DpTable &t, int32_t
 }
 
 // ---- host staging: the device twins of a call's host buffers (the *_host entries) ----
-enum HostDir { H_IN, H_OUT, H_SCRATCH };   // copied in; copied back; device only (an info nobody reads)
+// copied in; copied back; copied in and back; device only (an info nobody reads)
+enum HostDir { H_IN, H_OUT, H_INOUT, H_SCRATCH };
 struct HostBuf {
     void *host;      // NULL (an optional buffer the caller left out): no twin, unless H_SCRATCH
     size_t bytes;
@@ -311,7 +312,7 @@ struct HostStage {
         for (int i = 0; i < n; ++i) {
             if (!l[i].host && l[i].dir != H_SCRATCH) continue;
             if (int st = dev_alloc(dev[i], l[i].bytes, "hipMalloc (host staging)")) return st;
-            if (l[i].dir != H_IN) continue;
+            if (l[i].dir != H_IN && l[i].dir != H_INOUT) continue;
             const hipError_t e = hipMemcpy(dev[i].p, l[i].host, l[i].bytes, hipMemcpyHostToDevice);
             if (e != hipSuccess) return hip_err(e, "H2D");
         }
@@ -320,7 +321,7 @@ struct HostStage {
     int download(const HostBuf *l, int n) const
     {
         for (int i = 0; i < n; ++i) {
-            if (l[i].dir != H_OUT || !dev[i].p) continue;
+            if ((l[i].dir != H_OUT && l[i].dir != H_INOUT) || !dev[i].p) continue;
             const hipError_t e = hipMemcpy(l[i].host, dev[i].p, l[i].bytes, hipMemcpyDeviceToHost);
             if (e != hipSuccess) return hip_err(e, "D2H");
         }
@@ -809,8 +810,9 @@ int check_factor_args(const void *B, const void *R, const void *c, const void *P
     return 0;
 }
 
-// The arguments of lqrx_dp_resolve[_host] behind desc: A 2, B 3, c 4 (optional), fac 5, rhs 6
-int check_resolve_args(const void *A, const void *B, const void *c, const lqrx_dp_factors *fac, const lqrx_dp_rhs *rhs)
+// The dynamics and factors of lqrx_dp_resolve[_host] and lqrx_dp_resolve_box[_host] behind desc: A 2, B 3,
+// c 4 (optional), fac 5
+int check_resolve_factors(const void *A, const void *B, const void *c, const lqrx_dp_factors *fac)
 {
     if (!A) return set_err(-2, "pointer 2 (A) is NULL");
     if (!B) return set_err(-3, "pointer 3 (B) is NULL");
@@ -819,6 +821,13 @@ int check_resolve_args(const void *A, const void *B, const void *c, const lqrx_d
     if (!fac->Einv) return set_err(-5, "fac->Einv is NULL");
     if (c && !fac->Pc) return set_err(-5, "fac->Pc is NULL and c is given");
     if (!c && fac->Pc) return set_err(-5, "fac->Pc is given and c is NULL");
+    return 0;
+}
+
+// The arguments of lqrx_dp_resolve[_host] behind desc: A 2, B 3, c 4 (optional), fac 5, rhs 6
+int check_resolve_args(const void *A, const void *B, const void *c, const lqrx_dp_factors *fac, const lqrx_dp_rhs *rhs)
+{
+    if (int st = check_resolve_factors(A, B, c, fac)) return st;
     if (!rhs) return set_err(-6, "pointer 6 (rhs) is NULL");
     if (rhs->S < 1) return set_err(-6, "rhs->S must be >= 1 (got %lld)", (long long)rhs->S);
     if (!rhs->d && !rhs->p && !rhs->X && !rhs->U)
@@ -826,6 +835,27 @@ int check_resolve_args(const void *A, const void *B, const void *c, const lqrx_d
     if (!rhs->d && (rhs->X || rhs->U))
         return set_err(-6, "rhs->d is NULL and rhs->%s is asked for: d carries the backward pass to the forward one",
                        rhs->X ? "X" : "U");
+    return 0;
+}
+
+// The arguments of lqrx_dp_resolve_box[_host] behind desc: A 2, B 3, c 4 (optional), fac 5, rhs 6, box 7
+int check_box_args(const void *A, const void *B, const void *c, const lqrx_dp_factors *fac, const lqrx_dp_rhs *rhs,
+                   const lqrx_dp_box *box)
+{
+    if (int st = check_resolve_factors(A, B, c, fac)) return st;
+    if (!rhs) return set_err(-6, "pointer 6 (rhs) is NULL");
+    if (rhs->S < 1) return set_err(-6, "rhs->S must be >= 1 (got %lld)", (long long)rhs->S);
+    if (!rhs->d) return set_err(-6, "rhs->d is NULL: d carries the backward pass to the forward one");
+    if (rhs->p) return set_err(-6, "rhs->p must be NULL: the box entry forms no p");
+    if (!box) return set_err(-7, "pointer 7 (box) is NULL");
+    if (!(box->rho > 0) || !std::isfinite(box->rho)) return set_err(-7, "box->rho must be positive and finite (got %g)", box->rho);
+    if (!(box->relax >= 1 && box->relax < 2)) return set_err(-7, "box->relax must be in [1, 2) (got %g)", box->relax);
+    if (!(box->eps_prim >= 0)) return set_err(-7, "box->eps_prim must be >= 0 (got %g)", box->eps_prim);
+    if (!(box->eps_dual >= 0)) return set_err(-7, "box->eps_dual must be >= 0 (got %g)", box->eps_dual);
+    if (box->max_iter < 1 || box->max_iter > 10000)
+        return set_err(-7, "box->max_iter must be in 1 ... 10000 (got %d)", box->max_iter);
+    if (!box->Z) return set_err(-7, "box->Z is NULL");
+    if (!box->W) return set_err(-7, "box->W is NULL");
     return 0;
 }
 } // namespace
@@ -934,6 +964,75 @@ int lqrx_dp_resolve_host(const lqrx_dp_desc *d, const void *A, const void *B, co
     const lqrx_dp_factors dfac{dev[iK], dev[iE], dev[iPc]};
     const lqrx_dp_rhs drhs{rhs->S, dev[iq], dev[ir], dev[iqf], dev[ix0], dev[id], dev[ip], dev[iX], dev[iU]};
     st = lqrx_dp_resolve(d, dev[iA], dev[iB], dev[ic], &dfac, &drhs, nullptr);
+    if (st < 0) return st;
+    const int e = dev.download(hb, kBufs);
+    return e ? e : st;
+}
+
+// Input bounds by ADMM on the factors of one solve made with R + ρI (see lqrx.h): one kernel, no scratch
+int lqrx_dp_resolve_box(const lqrx_dp_desc *d, const void *A, const void *B, const void *c, const lqrx_dp_factors *fac,
+                        const lqrx_dp_rhs *rhs, const lqrx_dp_box *box, void *stream)
+{
+    int st = validate_dp_resolve(d, "lqrx_dp_resolve_box");
+    if (st) return st;
+    if (d->batch == 0) return 0;
+    if ((st = check_box_args(A, B, c, fac, rhs, box))) return st;
+    lqrx::DpBoxArgs a{};
+    a.A = A; a.B = B; a.c = c; a.K = fac->K; a.Einv = fac->Einv; a.Pc = fac->Pc;
+    a.q = rhs->q; a.r = rhs->r; a.qf = rhs->qf; a.x0 = rhs->x0;
+    a.u_lo = box->u_lo; a.u_hi = box->u_hi;
+    a.d = rhs->d; a.X = rhs->X; a.U = rhs->U; a.Z = box->Z; a.W = box->W; a.res = box->res; a.iters = box->iters;
+    a.rho = box->rho; a.relax = box->relax; a.eps_prim = box->eps_prim; a.eps_dual = box->eps_dual;
+    a.max_iter = box->max_iter;
+    a.n = d->n; a.m = d->m; a.N = d->N; a.dtype = d->dtype;
+    a.tv_AB = (int)d->knot_stride_AB; a.tv_QR = (int)d->knot_stride_QR;
+    a.batch = d->batch; a.S = rhs->S;
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = lqrx::dp_box_launch(a, s);
+    if (e != hipSuccess) return hip_err(e, "box kernel launch");
+    if (stream == nullptr && (e = hipStreamSynchronize(nullptr)) != hipSuccess) return hip_err(e, "box kernel");
+    return 0;
+}
+
+int lqrx_dp_resolve_box_host(const lqrx_dp_desc *d, const void *A, const void *B, const void *c,
+                             const lqrx_dp_factors *fac, const lqrx_dp_rhs *rhs, const lqrx_dp_box *box)
+{
+    int st = validate_dp_resolve(d, "lqrx_dp_resolve_box_host");
+    if (st) return st;
+    if (d->batch == 0) return 0;
+    if ((st = check_box_args(A, B, c, fac, rhs, box))) return st;
+    const size_t es = dsize(d->dtype), bt = (size_t)d->batch, n = d->n, m = d->m, N = d->N, S = (size_t)rhs->S;
+    const size_t kAB = d->knot_stride_AB ? N - 1 : 1, kQR = d->knot_stride_QR ? N - 1 : 1;
+    enum { iA, iB, ic, iK, iE, iPc, iq, ir, iqf, ix0, ilo, ihi, iZ, iW, id, iX, iU, iit, ires, kBufs };
+    static_assert(kBufs <= DpTable::kMaxRows + 1, "HostStage holds kMaxRows + 1 twins");
+    HostBuf hb[kBufs];
+    hb[iA] = host_in(A, n * n * kAB * es * bt);
+    hb[iB] = host_in(B, n * m * kAB * es * bt);
+    hb[ic] = host_in(c, n * kAB * es * bt);
+    hb[iK] = host_in(fac->K, m * n * (N - 1) * es * bt);
+    hb[iE] = host_in(fac->Einv, m * m * (N - 1) * es * bt);
+    hb[iPc] = host_in(fac->Pc, n * (N - 1) * es * bt);
+    hb[iq] = host_in(rhs->q, n * kQR * S * es * bt);
+    hb[ir] = host_in(rhs->r, m * kQR * S * es * bt);
+    hb[iqf] = host_in(rhs->qf, n * S * es * bt);
+    hb[ix0] = host_in(rhs->x0, n * S * es * bt);
+    hb[ilo] = host_in(box->u_lo, m * es * bt);
+    hb[ihi] = host_in(box->u_hi, m * es * bt);
+    hb[iZ] = HostBuf{box->Z, m * (N - 1) * S * es * bt, H_INOUT};
+    hb[iW] = HostBuf{box->W, m * (N - 1) * S * es * bt, H_INOUT};
+    hb[id] = HostBuf{rhs->d, m * (N - 1) * S * es * bt, H_OUT};   // only the outputs asked for have a twin
+    hb[iX] = HostBuf{rhs->X, n * N * S * es * bt, H_OUT};
+    hb[iU] = HostBuf{rhs->U, m * (N - 1) * S * es * bt, H_OUT};
+    hb[iit] = HostBuf{box->iters, 4 * S * bt, H_OUT};
+    hb[ires] = HostBuf{box->res, 2 * S * es * bt, H_OUT};
+    HostStage dev;
+    if ((st = dev.upload(hb, kBufs))) return st;
+    const lqrx_dp_factors dfac{dev[iK], dev[iE], dev[iPc]};
+    const lqrx_dp_rhs drhs{rhs->S, dev[iq], dev[ir], dev[iqf], dev[ix0], dev[id], nullptr, dev[iX], dev[iU]};
+    lqrx_dp_box dbox = *box;
+    dbox.u_lo = dev[ilo]; dbox.u_hi = dev[ihi]; dbox.Z = dev[iZ]; dbox.W = dev[iW];
+    dbox.iters = (int32_t *)dev[iit]; dbox.res = dev[ires];
+    st = lqrx_dp_resolve_box(d, dev[iA], dev[iB], dev[ic], &dfac, &drhs, &dbox, nullptr);
     if (st < 0) return st;
     const int e = dev.download(hb, kBufs);
     return e ? e : st;

@@ -29,76 +29,13 @@
 // first one met is the largest k) and that knot's E⁻¹ is written as zeros.  No atomics in either
 // kernel: the same bits from run to run.
 #include "lqrx_internal.h"
+#include "lqrx_resolve_ops.h"
 #include "lqrx_scen_ops.h"
 #include "lqrx_tile.h"
 #include "lqrx_wg.h"
 
 namespace lqrx {
 namespace {
-
-constexpr int RS_COLS = 16;   // right-hand sides per wave (the columns of a tile)
-
-// D1[i] += Σ_k M1[k][i]ᵀ Y[k] and D2[i] (+|−)= Σ_k M2[k][i]ᵀ Y[k], two TN chains on one B operand, in
-// mma_tn's order (k-tile, k-slice outermost) with the two products' MFMAs alternating
-template <typename T, int KT, int I1, int I2, bool NEG2>
-__device__ __forceinline__ void tn_pair(typename Tile<T>::acc (&D1)[I1], const typename Tile<T>::acc (&M1)[KT][I1],
-                                        typename Tile<T>::acc (&D2)[I2], const typename Tile<T>::acc (&M2)[KT][I2],
-                                        const typename Tile<T>::acc (&Y)[KT])
-{
-#pragma unroll
-    for (int k = 0; k < KT; ++k)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-#pragma unroll
-            for (int i = 0; i < I1; ++i) D1[i] = Tile<T>::mma(M1[k][i][r], Y[k][r], D1[i]);
-#pragma unroll
-            for (int i = 0; i < I2; ++i)
-                D2[i] = NEG2 ? Tile<T>::mma_nega(M2[k][i][r], Y[k][r], D2[i]) : Tile<T>::mma(M2[k][i][r], Y[k][r], D2[i]);
-        }
-}
-
-template <typename T, int I, int J>
-__device__ __forceinline__ void tiles_copy(typename Tile<T>::acc (&dst)[I][J], const typename Tile<T>::acc (&src)[I][J])
-{
-#pragma unroll
-    for (int i = 0; i < I; ++i)
-#pragma unroll
-        for (int j = 0; j < J; ++j) dst[i][j] = src[i][j];
-}
-
-template <typename T, int I>
-__device__ __forceinline__ void vec_copy(typename Tile<T>::acc (&dst)[I], const typename Tile<T>::acc (&src)[I])
-{
-#pragma unroll
-    for (int i = 0; i < I; ++i) dst[i] = src[i];
-}
-
-// d_{t,k}: this lane's column ↔ m elements at dk.  The store of the backward pass and the load of the
-// forward pass use this one map (no __restrict__: the load reads what the store wrote).
-template <typename T, int IT>
-__device__ __forceinline__ void d_store(const typename Tile<T>::acc (&D)[IT], T *dk, int rows, int lane, bool live)
-{
-#pragma unroll
-    for (int it = 0; it < IT; ++it)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = it * 16 + Tile<T>::row(lane, r);
-            if (live && row < rows) dk[row] = D[it][r];
-        }
-}
-template <typename T, int IT>
-__device__ __forceinline__ void d_load(typename Tile<T>::acc (&D)[IT], const T *dk, int rows, int lane, bool live)
-{
-#pragma unroll
-    for (int it = 0; it < IT; ++it)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = it * 16 + Tile<T>::row(lane, r);
-            const bool ok = live && row < rows;
-            const T x = dk[ok ? row : 0];
-            D[it][r] = ok ? x : T(0);
-        }
-}
 
 // TV: A, B, c per knot.  PF: the next knot's K_k, E_k⁻¹ (A_k, B_k with TV) and vectors are loaded one
 // knot ahead into a second set of registers; without it they are loaded at the top of their own knot.
@@ -306,12 +243,6 @@ __global__ __launch_bounds__(wg::BT) void dp_factor_kernel(const DpFactorArgs a)
         if (tid == 0 && a.info) a.info[b] = s_info;
         __syncthreads();
     }
-}
-
-inline unsigned resolve_grid(int64_t items)
-{
-    const int64_t cap = 1 << 20;   // the kernels loop over their work items with a grid stride
-    return (unsigned)(items < cap ? items : cap);
 }
 
 template <typename T, int NT, int MT>

@@ -203,6 +203,29 @@ struct DpResolveArgs {
 hipError_t dp_resolve_launch(const DpResolveArgs &a, hipStream_t s);
 bool dp_resolve_supported(int n, int m);
 
+// ---- input bounds by ADMM on the re-solve factors (lqrx_dp_box.hip), the support of the re-solve ----
+// Per instance t = b·S + j, iteration 1 … max_iter: r̂_k = r_{t,k} − ρ(z_k − w_k), the re-solve recursion on
+// (q, r̂, qf, x0) with the factors of R + ρI, û = αu + (1 − α)z, z⁺ = min(max(û + w, u_lo_b), u_hi_b),
+// w⁺ = w + û − z⁺; the instance stops after the first iteration with max‖u − z⁺‖∞ ≤ eps_prim and
+// ρ·max‖z⁺ − z‖∞ ≤ eps_dual (an eps of 0 never stops early; a NaN never stops).  The first two rows as in
+// DpResolveArgs.  u_lo, u_hi (m per problem) may be null (no bound); d, Z, W (m·(N−1) per instance,
+// Z and W in/out) are required; X, U, iters (per instance), res (2 per instance) may be null.
+// One kernel, no scratch.
+struct DpBoxArgs {
+    const void *A, *B, *c, *K, *Einv, *Pc;
+    const void *q, *r, *qf, *x0;
+    const void *u_lo, *u_hi;
+    void *d, *X, *U, *Z, *W, *res;
+    int32_t *iters;
+    double rho, relax, eps_prim, eps_dual;
+    int max_iter;
+    int n, m, N;
+    int dtype; // 0 f64, 1 f32
+    int tv_AB, tv_QR;
+    int64_t batch, S;
+};
+hipError_t dp_box_launch(const DpBoxArgs &a, hipStream_t s);
+
 struct KktArgs {
     const double *Y, *y, *H, *g; // device, packed per trajectory
     double *dz, *lam;

@@ -8,14 +8,14 @@ the reference's Julia surface.
 """
 from . import _lib
 from ._lib import F32, F64, LqrxError, load
-from .dp import (DPSolver, LQRBatch, LQRProblem, LQRSolution, compute_ctg, compute_gain, dp_factor_device,
-                 dp_resolve_device, dp_rollout_device, dp_solve_device, factor_batch, random_batch, resolve_batch,
-                 rollout_batch, solve, solve_batch)
+from .dp import (DPSolver, LQRBatch, LQRProblem, LQRSolution, box_batch, compute_ctg, compute_gain, dp_box_device,
+                 dp_factor_device, dp_resolve_device, dp_rollout_device, dp_solve_device, factor_batch, random_batch,
+                 resolve_batch, rollout_batch, solve, solve_batch)
 from .autograd import dp_adjoint_device, lqr_solve
 from .ls import LeastSquaresSolver, Primals
 
 __all__ = ["F32", "F64", "LqrxError", "load", "DPSolver", "LQRBatch", "LQRProblem",
            "LQRSolution", "solve", "solve_batch", "random_batch", "dp_solve_device",
            "rollout_batch", "dp_rollout_device", "factor_batch", "resolve_batch", "dp_factor_device",
-           "dp_resolve_device", "compute_gain", "compute_ctg", "dp_adjoint_device", "lqr_solve",
-           "LeastSquaresSolver", "Primals"]
+           "dp_resolve_device", "box_batch", "dp_box_device", "compute_gain", "compute_ctg", "dp_adjoint_device",
+           "lqr_solve", "LeastSquaresSolver", "Primals"]

@@ -71,6 +71,14 @@ class DpRhs(C.Structure):
     _fields_ = [("S", C.c_int64)] + [(k, C.c_void_p) for k in ("q", "r", "qf", "x0", "d", "p", "X", "U")]
 
 
+class DpBox(C.Structure):
+    """Mirror of ``lqrx_dp_box`` (rho, relax, eps_prim, eps_dual, max_iter; u_lo, u_hi optional in; Z, W
+    in/out and required; iters, res optional out)."""
+
+    _fields_ = ([(k, C.c_double) for k in ("rho", "relax", "eps_prim", "eps_dual")] + [("max_iter", C.c_int32)]
+                + [(k, C.c_void_p) for k in ("u_lo", "u_hi", "Z", "W", "iters", "res")])
+
+
 class KktDesc(C.Structure):
     """Mirror of ``lqrx_kkt_desc``."""
 
@@ -156,6 +164,10 @@ _SIGS = {
     "lqrx_dp_factor_host": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 7),
     "lqrx_dp_resolve": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 3 + [C.POINTER(DpFactors), C.POINTER(DpRhs), _VP]),
     "lqrx_dp_resolve_host": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 3 + [C.POINTER(DpFactors), C.POINTER(DpRhs)]),
+    "lqrx_dp_resolve_box": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 3
+                            + [C.POINTER(DpFactors), C.POINTER(DpRhs), C.POINTER(DpBox), _VP]),
+    "lqrx_dp_resolve_box_host": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 3
+                                 + [C.POINTER(DpFactors), C.POINTER(DpRhs), C.POINTER(DpBox)]),
     "lqrx_dp_solve_adjoint": (C.c_int, [C.POINTER(DpDesc)] + [_VP] * 9 + [C.POINTER(DpGrad)]
                               + [_VP, _VP]),
     "lqrx_kkt_solve_host_devices": (C.c_int, [C.POINTER(KktDesc)] + [_VP] * 7 + [_VP, C.c_int32]),

@@ -31,7 +31,7 @@ from . import _lib
 __all__ = ["LQRProblem", "LQRSolution", "DPSolver", "solve", "solve_batch", "LQRBatch",
            "random_batch", "to_abi", "from_abi", "dp_solve_device", "compute_gain", "compute_ctg",
            "compute_ctg_batch", "rollout_batch", "dp_rollout_device", "factor_batch", "resolve_batch",
-           "dp_factor_device", "dp_resolve_device"]
+           "dp_factor_device", "dp_resolve_device", "box_batch", "dp_box_device"]
 
 
 def to_abi(a: np.ndarray) -> np.ndarray:
@@ -738,4 +738,156 @@ def dp_resolve_device(t: dict, N: int, fac: dict, rhs: dict, stream: int | None 
                                                 C.byref(rs), C.c_void_p(stream) if stream else None))
     res = {k: out[k] for k in outputs}
     res["rc"] = rc
+    return res
+
+
+_BOX_RHS_OUT = ("d", "X", "U")
+_BOX_OUT = ("iters", "res")
+
+
+def _box_params(who: str, rho, relax, eps, max_iter) -> tuple:
+    try:
+        eps_prim, eps_dual = (float(e) for e in eps)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: eps is the pair (eps_prim, eps_dual) (got {eps!r})") from None
+    return float(rho), float(relax), eps_prim, eps_dual, int(max_iter)
+
+
+def box_batch(b: LQRBatch, u_lo, u_hi, x0=None, q=None, r=None, qf=None, rho: float = 1.0, relax: float = 1.6,
+              eps=(1e-6, 1e-6), max_iter: int = 500, Z=None, W=None, dtype: int = _lib.F64) -> dict:
+    """Input bounds u_lo ≤ u_k ≤ u_hi on S instances per problem, the whole way on logical host arrays:
+    the cross solve of b with R + ρI (on every stored R knot) and all P_k, factor_batch, then
+    lqrx_dp_resolve_box_host (include/lqrx.h has the iteration).
+
+    u_lo, u_hi: (batch, m), (m,), a scalar, or None (no bound on that side); ±inf allowed.  x0, qf
+    (batch, S, n); q (batch, S, n) or (batch, S, N−1, n); r (batch, S, m) or (batch, S, N−1, m), a knot axis
+    on both or neither; each may be None (zero).  With all four None the batch's own x0, q, r, qf are
+    the one instance (S = 1).  Z, W (batch, S, N−1, m) warm-start the iteration (None: zeros, a cold start)
+    and are not modified.  eps = (eps_prim, eps_dual).  Returns X (batch, S, N, n), U, Z, W, Y = ρW
+    (batch, S, N−1, m), iters (batch, S), res (batch, S, 2: r_prim, r_dual), info (batch: the solve's or
+    the factor's, 0 when R + ρI gave positive definite E_k) and rc."""
+    n, m, N = b.size()
+    bt = b.batch
+    tvAB, tvQR_b = b.time_varying()
+    npdt = np.float64 if dtype == _lib.F64 else np.float32
+    rho, relax, eps_prim, eps_dual, max_iter = _box_params("box_batch", rho, relax, eps, max_iter)
+    if not (rho > 0 and np.isfinite(rho)):
+        raise ValueError(f"box_batch: rho must be positive and finite (got {rho})")
+    given = {k: np.asarray(v, dtype=npdt) for k, v in dict(x0=x0, q=q, r=r, qf=qf).items() if v is not None}
+    if not given:   # the batch's own right-hand side, one instance per problem
+        own = dict(x0=b.x0, q=b.q, r=b.r, qf=b.qf)
+        given = {k: np.asarray(v, dtype=npdt)[:, None] for k, v in own.items() if v is not None}
+    first = next(iter(given.values()))
+    S = first.shape[1] if first.ndim >= 2 else 0
+    if S < 1:
+        raise ValueError("box_batch: right-hand sides are (batch, S, ...) with S >= 1")
+    for k in ("x0", "qf"):
+        if k in given and given[k].shape != (bt, S, n):
+            raise ValueError(f"box_batch: {k} is (batch, S, n) = {(bt, S, n)} (got {given[k].shape})")
+    knot = {k: given[k].ndim == 4 for k in ("q", "r") if k in given}
+    if len(set(knot.values())) > 1:
+        raise ValueError("box_batch: q and r carry a knot axis (batch, S, N-1, ·) both or neither")
+    tvQR = int(any(knot.values()))
+    for k, w in (("q", n), ("r", m)):
+        want = (bt, S, N - 1, w) if tvQR else (bt, S, w)
+        if k in given and given[k].shape != want:
+            raise ValueError(f"box_batch: {k} is {want} (got {given[k].shape})")
+    bounds = {}
+    for k, v in (("u_lo", u_lo), ("u_hi", u_hi)):
+        if v is None:
+            bounds[k] = None
+            continue
+        try:
+            bounds[k] = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=npdt), (bt, m))).reshape(-1)
+        except ValueError:
+            raise ValueError(f"box_batch: {k} is (batch, m) = {(bt, m)}, (m,) or a scalar (got {np.shape(v)})") from None
+    zw = {}
+    for k, v in (("Z", Z), ("W", W)):
+        if v is None:
+            zw[k] = np.zeros(bt * S * (N - 1) * m, npdt)
+        elif np.shape(v) != (bt, S, N - 1, m):
+            raise ValueError(f"box_batch: {k} is (batch, S, N-1, m) = {(bt, S, N - 1, m)} (got {np.shape(v)})")
+        else:
+            zw[k] = np.array(v, dtype=npdt).reshape(-1)
+    # one solve with R + ρI on every stored R knot, every P_k kept, and its factors
+    R = np.asarray(b.R, dtype=np.float64)
+    br = replace(b, R=R + rho * np.eye(m), M=b.M if b.M is not None else np.zeros(R.shape[:-2] + (m, n)))
+    sol = solve_batch(br, dtype=dtype, all_P=True)
+    fac = factor_batch(br, sol["P"], dtype=dtype)
+    info = np.where(sol["info"] != 0, sol["info"], fac["info"]).astype(np.int32)
+    flat = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a, dtype=npdt)).reshape(-1)
+    mat = lambda a: None if a is None else to_abi(np.asarray(a, dtype=npdt)).reshape(-1)
+    ins = dict(A=mat(b.A), B=mat(b.B), c=flat(b.c), K=mat(sol["K"]), Einv=mat(fac["Einv"]), Pc=flat(fac["Pc"]))
+    rh = {k: flat(given.get(k)) for k in ("q", "r", "qf", "x0")}
+    out = dict(d=np.zeros(bt * S * (N - 1) * m, npdt), X=np.zeros(bt * S * N * n, npdt), U=np.zeros(bt * S * (N - 1) * m, npdt))
+    iters = np.zeros(bt * S, np.int32)
+    res = np.zeros(bt * S * 2, npdt)
+    p = lambda a: None if a is None else a.ctypes.data
+    fc = _lib.DpFactors(p(ins["K"]), p(ins["Einv"]), p(ins["Pc"]))
+    rs = _lib.DpRhs(S, *[p(rh[k]) for k in ("q", "r", "qf", "x0")], p(out["d"]), None, p(out["X"]), p(out["U"]))
+    bx = _lib.DpBox(rho, relax, eps_prim, eps_dual, max_iter, p(bounds["u_lo"]), p(bounds["u_hi"]), p(zw["Z"]), p(zw["W"]),
+                    p(iters), p(res))
+    desc = _lib.DpDesc(n, m, N, dtype, bt, 0, 0, tvAB, tvQR)
+    rc = _lib.check(_lib.load().lqrx_dp_resolve_box_host(C.byref(desc), p(ins["A"]), p(ins["B"]), p(ins["c"]),
+                                                         C.byref(fc), C.byref(rs), C.byref(bx)))
+    sh = (bt, S, N - 1, m)
+    Wo = zw["W"].reshape(sh)
+    return dict(X=out["X"].reshape(bt, S, N, n), U=out["U"].reshape(sh), Z=zw["Z"].reshape(sh), W=Wo, Y=npdt(rho) * Wo,
+                iters=iters.reshape(bt, S), res=res.reshape(bt, S, 2), info=info, rc=rc)
+
+
+def dp_box_device(t: dict, N: int, fac: dict, rhs: dict, box: dict, stream: int | None = None,
+                  out: dict | None = None) -> dict:
+    """Device-pointer entry point of lqrx_dp_resolve_box on torch tensors already in ABI layout (flat,
+    layout 0), in the manner of dp_resolve_device.
+
+    t, fac as in dp_resolve_device; the factors are those of a solve with R + ρI.  rhs = dict(S=, q=, r=,
+    qf=, x0=, tv_QR=, outputs=("d", "X", "U")): d is always among the outputs.  box = dict(rho=, relax=1.6,
+    eps_prim=1e-6, eps_dual=1e-6, max_iter=500, u_lo=, u_hi=, Z=, W=, outputs=("iters", "res")): u_lo, u_hi
+    (m·batch) optional; Z, W (m·(N−1)·S·batch, required) are updated in place: zeros are a cold start.
+    `out` may hold preallocated d, X, U, iters (int32, S·batch), res (2·S·batch).  Returns the dict of the
+    outputs asked for, Z, W and rc.  `stream` is a raw hipStream_t; None = the null stream, synchronous.
+    The call allocates nothing inside the library."""
+    import torch
+
+    outputs = tuple(rhs.get("outputs", _BOX_RHS_OUT))
+    if "d" not in outputs or any(k not in _BOX_RHS_OUT for k in outputs):
+        raise ValueError(f"dp_box_device: rhs outputs name d and any of {_BOX_RHS_OUT[1:]} (got {outputs})")
+    box_out = tuple(box.get("outputs", _BOX_OUT))
+    if any(k not in _BOX_OUT for k in box_out):
+        raise ValueError(f"dp_box_device: box outputs name any of {_BOX_OUT} (got {box_out})")
+    n, m, bt = t["n"], t["m"], t["batch"]
+    tdt = t["A"].dtype
+    dtype = _lib.F64 if tdt == torch.float64 else _lib.F32
+    dev = t["A"].device
+    S = int(rhs["S"])
+    if box.get("rho") is None:
+        raise ValueError("dp_box_device: box needs rho, the ρ of the solve the factors come from")
+    rho, relax, eps_prim, eps_dual, max_iter = _box_params(
+        "dp_box_device", box["rho"], box.get("relax", 1.6), (box.get("eps_prim", 1e-6), box.get("eps_dual", 1e-6)),
+        box.get("max_iter", 500))
+    for k in ("Z", "W"):
+        if box.get(k) is None or box[k].numel() != bt * S * (N - 1) * m or box[k].dtype != tdt:
+            raise ValueError(f"dp_box_device: box[{k!r}] is a tensor of m·(N−1)·S·batch = {bt * S * (N - 1) * m} elements "
+                             f"of the problem's dtype (zeros: a cold start)")
+    for k in ("u_lo", "u_hi"):
+        if box.get(k) is not None and box[k].numel() != bt * m:
+            raise ValueError(f"dp_box_device: box[{k!r}] has {box[k].numel()} elements, expected m·batch = {bt * m}")
+    sizes = dict(d=bt * S * (N - 1) * m, X=bt * S * N * n, U=bt * S * (N - 1) * m, iters=bt * S, res=2 * bt * S)
+    out = {} if out is None else out
+    for k in outputs + box_out:
+        if out.get(k) is None:
+            out[k] = torch.empty(sizes[k], dtype=torch.int32 if k == "iters" else tdt, device=dev)
+    p = lambda x: None if x is None else x.data_ptr()
+    fc = _lib.DpFactors(p(fac.get("K")), p(fac.get("Einv")), p(fac.get("Pc")))
+    rs = _lib.DpRhs(S, *[p(rhs.get(k)) for k in ("q", "r", "qf", "x0")], p(out["d"]), None,
+                    *[p(out[k]) if k in outputs else None for k in ("X", "U")])
+    bx = _lib.DpBox(rho, relax, eps_prim, eps_dual, max_iter, p(box.get("u_lo")), p(box.get("u_hi")), p(box["Z"]),
+                    p(box["W"]), *[p(out[k]) if k in box_out else None for k in _BOX_OUT])
+    desc = _lib.DpDesc(n, m, N, dtype, bt, 0, 0, int(t.get("tv_AB", 0)), int(rhs.get("tv_QR", 0)))
+    vp = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+    rc = _lib.check(_lib.load().lqrx_dp_resolve_box(C.byref(desc), vp(t["A"]), vp(t["B"]), vp(t.get("c")), C.byref(fc),
+                                                    C.byref(rs), C.byref(bx), C.c_void_p(stream) if stream else None))
+    res = {k: out[k] for k in outputs + box_out}
+    res.update(Z=box["Z"], W=box["W"], rc=rc)
     return res

@@ -63,14 +63,14 @@ __global__ __launch_bounds__(64) void dp_box_kernel(const DpBoxArgs a)
 {
     using acc = typename Tile<T>::acc;
     const int lane = threadIdx.x, n = a.n, m = a.m, N = a.N;
-    const int64_t tiles = (a.S + RS_COLS - 1) / RS_COLS, total = a.batch * tiles;
+    const int64_t tiles = (a.S + DP_COLS - 1) / DP_COLS, total = a.batch * tiles;
     const int64_t nn = (int64_t)n * n, nm = (int64_t)n * m, mm = (int64_t)m * m;
     const int64_t kab = TV ? N - 1 : 1, kqr = a.tv_QR ? N - 1 : 1;
     const T rho = (T)a.rho, alpha = (T)a.relax, om = T(1) - alpha, eps_p = (T)a.eps_prim, eps_d = (T)a.eps_dual;
     const bool stops = a.eps_prim > 0 && a.eps_dual > 0;   // an eps of 0 never stops early
     const T inf = std::numeric_limits<T>::infinity();
     for (int64_t wi = blockIdx.x; wi < total; wi += gridDim.x) {
-        const int64_t b = wi / tiles, j = (wi - b * tiles) * RS_COLS + tcol(lane);
+        const int64_t b = wi / tiles, j = (wi - b * tiles) * DP_COLS + tcol(lane);
         const bool live = j < a.S;
         const int64_t t = b * a.S + (live ? j : 0);   // a dead column addresses instance 0 and selects zero
         const T *Ab = (const T *)a.A + b * nn * kab, *Bb = (const T *)a.B + b * nm * kab;
@@ -261,7 +261,7 @@ __global__ __launch_bounds__(64) void dp_box_kernel(const DpBoxArgs a)
             active = active && !(stops && rp <= eps_p && rd <= eps_d);   // false on a NaN: it never converges
             if (!__any(active)) break;                                      // wave-uniform
         }
-        if (live && lane < RS_COLS) {
+        if (live && lane < DP_COLS) {
             if (a.iters) a.iters[t] = iters;
             if (a.res) {
                 ((T *)a.res)[2 * t] = res_p;
@@ -271,7 +271,7 @@ __global__ __launch_bounds__(64) void dp_box_kernel(const DpBoxArgs a)
     }
 }
 
-// PF as resolve_launch_tiles sets it (fp64 at n = 64 and at 2×2 tiles has no room for a second set of
+// PF as resolve_launch_t sets it (fp64 at n = 64 and at 2×2 tiles has no room for a second set of
 // per-knot operands), and off at NT = 4 in fp32 as well: with it those four instantiations spill 108 –
 // 1092 B per lane, without it only the time-varying 4×2 one does (456 B).  No NT ≤ 2 instantiation
 // spills; fp64 NT = 4 spills either way, as in the re-solve (profiles/r14/box/resource_usage.txt).
@@ -280,24 +280,18 @@ template <typename T, int NT, int MT, bool TV> constexpr bool box_prefetch()
     return !(sizeof(T) == 8 && NT * MT >= 4) && NT < 4;
 }
 
-template <typename T, int NT, int MT>
-hipError_t box_launch_tiles(const DpBoxArgs &a, hipStream_t s)
-{
-    const unsigned grid = resolve_grid(a.batch * ((a.S + RS_COLS - 1) / RS_COLS));
-    return with_bool(a.tv_AB != 0, [&](auto tv) {
-        constexpr bool TV = decltype(tv)::value;
-        dp_box_kernel<T, NT, MT, TV, box_prefetch<T, NT, MT, TV>()><<<grid, 64, 0, s>>>(a);
-        return hipGetLastError();
-    });
-}
-
 template <typename T>
 hipError_t box_launch_t(const DpBoxArgs &a, hipStream_t s)
 {
-    const int nt = a.n <= 16 ? 1 : a.n <= 32 ? 2 : 4, mt = a.m <= 16 ? 1 : 2;
-    if (nt == 1) return mt == 1 ? box_launch_tiles<T, 1, 1>(a, s) : box_launch_tiles<T, 1, 2>(a, s);
-    if (nt == 2) return mt == 1 ? box_launch_tiles<T, 2, 1>(a, s) : box_launch_tiles<T, 2, 2>(a, s);
-    return mt == 1 ? box_launch_tiles<T, 4, 1>(a, s) : box_launch_tiles<T, 4, 2>(a, s);
+    const unsigned grid = dp_grid(a.batch * ((a.S + DP_COLS - 1) / DP_COLS));
+    return with_tiles(a.n, a.m, [&](auto nt, auto mt) {
+        return with_bool(a.tv_AB != 0, [&](auto tv) {
+            constexpr int NT = decltype(nt)::value, MT = decltype(mt)::value;
+            constexpr bool TV = decltype(tv)::value;
+            dp_box_kernel<T, NT, MT, TV, box_prefetch<T, NT, MT, TV>()><<<grid, 64, 0, s>>>(a);
+            return hipGetLastError();
+        });
+    });
 }
 
 } // namespace

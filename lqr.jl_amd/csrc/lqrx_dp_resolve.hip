@@ -44,11 +44,11 @@ __global__ __launch_bounds__(64) void dp_resolve_kernel(const DpResolveArgs a)
 {
     using acc = typename Tile<T>::acc;
     const int lane = threadIdx.x, n = a.n, m = a.m, N = a.N;
-    const int64_t tiles = (a.S + RS_COLS - 1) / RS_COLS, total = a.batch * tiles;
+    const int64_t tiles = (a.S + DP_COLS - 1) / DP_COLS, total = a.batch * tiles;
     const int64_t nn = (int64_t)n * n, nm = (int64_t)n * m, mm = (int64_t)m * m;
     const int64_t kab = TV ? N - 1 : 1, kqr = a.tv_QR ? N - 1 : 1, kp = a.p_all ? N : 1;
     for (int64_t wi = blockIdx.x; wi < total; wi += gridDim.x) {
-        const int64_t b = wi / tiles, j = (wi - b * tiles) * RS_COLS + tcol(lane);
+        const int64_t b = wi / tiles, j = (wi - b * tiles) * DP_COLS + tcol(lane);
         const bool live = j < a.S;
         const int64_t t = b * a.S + (live ? j : 0);   // a dead column addresses right-hand side 0 and selects zero
         const T *Ab = (const T *)a.A + b * nn * kab, *Bb = (const T *)a.B + b * nm * kab;
@@ -245,34 +245,28 @@ __global__ __launch_bounds__(wg::BT) void dp_factor_kernel(const DpFactorArgs a)
     }
 }
 
-template <typename T, int NT, int MT>
-hipError_t resolve_launch_tiles(const DpResolveArgs &a, hipStream_t s)
-{
-    const unsigned grid = resolve_grid(a.batch * ((a.S + RS_COLS - 1) / RS_COLS));
-    return with_bool(a.tv_AB != 0, [&](auto tv) {
-        constexpr bool TV = decltype(tv)::value;
-        // fp64 at n = 64 (A alone is 128 VGPRs in either operand form) and at 2×2 tiles: a second set of
-        // per-knot operands does not fit without spilling
-        constexpr bool PF = !(sizeof(T) == 8 && NT * MT >= 4);
-        dp_resolve_kernel<T, NT, MT, TV, PF><<<grid, 64, 0, s>>>(a);
-        return hipGetLastError();
-    });
-}
-
 template <typename T>
 hipError_t resolve_launch_t(const DpResolveArgs &a, hipStream_t s)
 {
-    const int nt = a.n <= 16 ? 1 : a.n <= 32 ? 2 : 4, mt = a.m <= 16 ? 1 : 2;
-    if (nt == 1) return mt == 1 ? resolve_launch_tiles<T, 1, 1>(a, s) : resolve_launch_tiles<T, 1, 2>(a, s);
-    if (nt == 2) return mt == 1 ? resolve_launch_tiles<T, 2, 1>(a, s) : resolve_launch_tiles<T, 2, 2>(a, s);
-    return mt == 1 ? resolve_launch_tiles<T, 4, 1>(a, s) : resolve_launch_tiles<T, 4, 2>(a, s);
+    const unsigned grid = dp_grid(a.batch * ((a.S + DP_COLS - 1) / DP_COLS));
+    return with_tiles(a.n, a.m, [&](auto nt, auto mt) {
+        return with_bool(a.tv_AB != 0, [&](auto tv) {
+            constexpr int NT = decltype(nt)::value, MT = decltype(mt)::value;
+            constexpr bool TV = decltype(tv)::value;
+            // fp64 at n = 64 (A alone is 128 VGPRs in either operand form) and at 2×2 tiles: a second set
+            // of per-knot operands does not fit without spilling
+            constexpr bool PF = !(sizeof(T) == 8 && NT * MT >= 4);
+            dp_resolve_kernel<T, NT, MT, TV, PF><<<grid, 64, 0, s>>>(a);
+            return hipGetLastError();
+        });
+    });
 }
 
 template <typename T>
 hipError_t factor_launch_t(const DpFactorArgs &a, hipStream_t s)
 {
     const size_t lds = ((size_t)a.n * a.m + 2 * (size_t)a.m * a.m) * sizeof(T);   // ≤ 32 768 B (n = 64, m = 32, fp64)
-    dp_factor_kernel<T><<<resolve_grid(a.batch), wg::BT, lds, s>>>(a);
+    dp_factor_kernel<T><<<dp_grid(a.batch), wg::BT, lds, s>>>(a);
     return hipGetLastError();
 }
 

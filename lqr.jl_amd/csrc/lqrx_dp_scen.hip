@@ -35,7 +35,6 @@
 namespace lqrx {
 namespace {
 
-constexpr int SC_COLS = 16;   // scenarios per wave of the MFMA kernel (the columns of a tile)
 constexpr int SW_COLS = 4;    // scenarios per workgroup of the wg kernel (one wave each)
 constexpr int SW_THREADS = 64 * SW_COLS;
 
@@ -82,12 +81,12 @@ __global__ __launch_bounds__(64) void dp_scen_kernel(const DpScenArgs a)
 {
     using acc = typename Tile<T>::acc;
     const int lane = threadIdx.x, n = a.n, m = a.m, N = a.N;
-    const int64_t tiles = (a.S + SC_COLS - 1) / SC_COLS, total = a.batch * tiles;
+    const int64_t tiles = (a.S + DP_COLS - 1) / DP_COLS, total = a.batch * tiles;
     const int64_t nn = (int64_t)n * n, nm = (int64_t)n * m, mm = (int64_t)m * m;
     const int64_t kab = TV ? N - 1 : 1, kqr = a.tv_QR ? N - 1 : 1;
     const T inf = std::numeric_limits<T>::infinity();
     for (int64_t wi = blockIdx.x; wi < total; wi += gridDim.x) {
-        const int64_t b = wi / tiles, j = (wi - b * tiles) * SC_COLS + tcol(lane);
+        const int64_t b = wi / tiles, j = (wi - b * tiles) * DP_COLS + tcol(lane);
         const bool live = j < a.S;
         const int64_t t = b * a.S + (live ? j : 0);   // a dead column addresses scenario 0 and selects zero
         const T *Ab = (const T *)a.A + b * nn * kab, *Bb = (const T *)a.B + b * nm * kab;
@@ -201,7 +200,7 @@ __global__ __launch_bounds__(64) void dp_scen_kernel(const DpScenArgs a)
             // the four lane groups that share a column, in a fixed order
             jl += __shfl_xor(jl, 16);
             jl += __shfl_xor(jl, 32);
-            if (live && lane < SC_COLS) ((T *)a.J)[t] = (T)jl;
+            if (live && lane < DP_COLS) ((T *)a.J)[t] = (T)jl;
         }
     }
 }
@@ -302,36 +301,24 @@ __global__ __launch_bounds__(SW_THREADS) void dp_scen_wg_kernel(const DpScenArgs
     }
 }
 
-inline unsigned scen_grid(int64_t items)
-{
-    const int64_t cap = 1 << 20;   // the kernels loop over their work items with a grid stride
-    return (unsigned)(items < cap ? items : cap);
-}
-
-template <typename T, int NT, int MT>
-hipError_t scen_launch_tiles(const DpScenArgs &a, hipStream_t s)
-{
-    const unsigned grid = scen_grid(a.batch * ((a.S + SC_COLS - 1) / SC_COLS));
-    return with_bools(a.tv_AB != 0, a.J != nullptr, [&](auto tv, auto cost) {
-        constexpr bool TV = decltype(tv)::value, COST = decltype(cost)::value;
-        // n = 64 in fp64: A and B alone are 192 VGPRs; a second set of per-knot operands does not fit
-        constexpr bool PF = !(sizeof(T) == 8 && NT == 4);
-        dp_scen_kernel<T, NT, MT, TV, COST, PF><<<grid, 64, 0, s>>>(a);
-        return hipGetLastError();
-    });
-}
-
 template <typename T>
 hipError_t scen_launch_t(const DpScenArgs &a, hipStream_t s)
 {
     const int n = a.n, m = a.m;
     if (n <= 64 && m <= 32) {
-        const int nt = n <= 16 ? 1 : n <= 32 ? 2 : 4, mt = m <= 16 ? 1 : 2;
-        if (nt == 1) return mt == 1 ? scen_launch_tiles<T, 1, 1>(a, s) : scen_launch_tiles<T, 1, 2>(a, s);
-        if (nt == 2) return mt == 1 ? scen_launch_tiles<T, 2, 1>(a, s) : scen_launch_tiles<T, 2, 2>(a, s);
-        return mt == 1 ? scen_launch_tiles<T, 4, 1>(a, s) : scen_launch_tiles<T, 4, 2>(a, s);
+        const unsigned grid = dp_grid(a.batch * ((a.S + DP_COLS - 1) / DP_COLS));
+        return with_tiles(n, m, [&](auto nt, auto mt) {
+            return with_bools(a.tv_AB != 0, a.J != nullptr, [&](auto tv, auto cost) {
+                constexpr int NT = decltype(nt)::value, MT = decltype(mt)::value;
+                constexpr bool TV = decltype(tv)::value, COST = decltype(cost)::value;
+                // n = 64 in fp64: A and B alone are 192 VGPRs; a second set of per-knot operands does not fit
+                constexpr bool PF = !(sizeof(T) == 8 && NT == 4);
+                dp_scen_kernel<T, NT, MT, TV, COST, PF><<<grid, 64, 0, s>>>(a);
+                return hipGetLastError();
+            });
+        });
     }
-    const unsigned grid = scen_grid(a.batch * ((a.S + SW_COLS - 1) / SW_COLS));
+    const unsigned grid = dp_grid(a.batch * ((a.S + SW_COLS - 1) / SW_COLS));
     const size_t lds = (size_t)SW_COLS * (2 * (size_t)n + m) * sizeof(T);   // ≤ 49 152 B (n = m = 512, fp64)
     if (a.J)
         dp_scen_wg_kernel<T, true><<<grid, SW_THREADS, lds, s>>>(a);

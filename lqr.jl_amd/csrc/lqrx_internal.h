@@ -70,6 +70,12 @@ template <typename F> hipError_t with_kind(int kind, F &&f)
          : kind == DP_AFFINE ? f(IntC<DP_AFFINE>{}) : kind == DP_CROSS ? f(IntC<DP_CROSS>{})
          : kind == DP_VALUE ? f(IntC<DP_VALUE>{}) : hipErrorInvalidValue;
 }
+// the register tiles of n ≤ 64 states and m ≤ 32 inputs: f(IntC<NT>, IntC<MT>), NT of 1, 2, 4 and MT of 1, 2
+template <typename F> hipError_t with_tiles(int n, int m, F &&f)
+{
+    const auto mt = [&](auto nt) { return m <= 16 ? f(nt, IntC<1>{}) : f(nt, IntC<2>{}); };
+    return n <= 16 ? mt(IntC<1>{}) : n <= 32 ? mt(IntC<2>{}) : mt(IntC<4>{});
+}
 hipError_t dp_launch(const DpArgs &a, hipStream_t s);
 // J = V_1(x0) = ½x0ᵀP_1x0 + p_1ᵀx0 + s_1 behind a value solve (lqrx_dp.hip): one thread per
 // trajectory on a's P, p, vs and x0 in a's layout, accumulated in double, written to J (batch)

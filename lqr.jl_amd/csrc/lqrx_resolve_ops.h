@@ -7,8 +7,6 @@
 
 namespace lqrx {
 
-constexpr int RS_COLS = 16;   // right-hand sides per wave (the columns of a tile)
-
 // D1[i] += Σ_k M1[k][i]ᵀ Y[k] and D2[i] (+|−)= Σ_k M2[k][i]ᵀ Y[k], two TN chains on one B operand, in
 // mma_tn's order (k-tile, k-slice outermost) with the two products' MFMAs alternating
 template <typename T, int KT, int I1, int I2, bool NEG2>
@@ -69,13 +67,6 @@ __device__ __forceinline__ void d_load(typename Tile<T>::acc (&D)[IT], const T *
             const T x = dk[ok ? row : 0];
             D[it][r] = ok ? x : T(0);
         }
-}
-
-// one wave per work item, the kernels loop over their work items with a grid stride
-inline unsigned resolve_grid(int64_t items)
-{
-    const int64_t cap = 1 << 20;
-    return (unsigned)(items < cap ? items : cap);
 }
 
 } // namespace lqrx

@@ -1,11 +1,20 @@
-// lqrx_scen_ops.h — the operand helpers of the kernels whose tile columns are scenarios or right-hand
-// sides (lqrx_dp_scen.hip, lqrx_dp_resolve.hip): X, U and their kin are C-layout tiles (lqrx_tile.h)
-// with one trajectory per column, so register r of such a tile is the B operand of k-slice r and a
-// matrix enters a product as A operands loaded straight from global memory.
+// lqrx_scen_ops.h — the operand helpers of the kernels whose tile columns are scenarios, right-hand
+// sides or ADMM instances (lqrx_dp_scen.hip, lqrx_dp_resolve.hip, lqrx_dp_box.hip): X, U and their kin
+// are C-layout tiles (lqrx_tile.h) with one trajectory per column, so register r of such a tile is the
+// B operand of k-slice r and a matrix enters a product as A operands loaded straight from global memory.
 #pragma once
 #include "lqrx_tile.h"
 
 namespace lqrx {
+
+constexpr int DP_COLS = 16;   // trajectories per wave (the columns of a tile)
+
+// one wave per work item, the kernels loop over their work items with a grid stride
+inline unsigned dp_grid(int64_t items)
+{
+    const int64_t cap = 1 << 20;
+    return (unsigned)(items < cap ? items : cap);
+}
 
 // A rows×cols column-major matrix (leading dimension rows) as the A operands of D[IT] += Mat·Y[KT]:
 // op[it][kt][r] = Mat(it·16 + (lane & 15), kt·16 + Tile<T>::row(lane, r)), zero past the matrix.  Loads

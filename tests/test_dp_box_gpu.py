@@ -349,6 +349,20 @@ def test_continuation_is_exact(lqrx, gpu_ok, prec):
         assert same_bits(ab[k], full[k]), k
 
 
+@pytest.mark.parametrize("prec", ["f64", "f32"])
+@pytest.mark.parametrize("shape", [(17, 5, 12, 3, True), (24, 18, 10, 3, False), (64, 32, 12, 2, False)], ids=sid)
+def test_first_cold_iteration_has_the_bits_of_the_resolve(lqrx, gpu_ok, shape, prec):
+    """Z = W = 0, max_iter = 1, eps = 0: r̂ = r − ρ·0 is r exactly, so d, X and U are the bits of lqrx_dp_resolve on
+    the same factors and right-hand sides: the two kernels compute one and the same pair of passes."""
+    c = case(lqrx, shape, prec, 21)
+    r = c.run(1)
+    ref = lqrx.dp_resolve_device(c.sv.t, shape[2], c.sv.facd,
+                                 dict(c.rhs, S=21, tv_QR=int(shape[4]), outputs=("d", "X", "U")))
+    assert (r["iters"] == 1).all().item()
+    for k in ("d", "X", "U"):
+        assert same_bits(r[k], ref[k]), k
+
+
 # ---- guard zones ----
 def _filled(like, sizes):
     return {k: pattern_filled(like, sz) for k, sz in sizes.items()}

@@ -289,6 +289,20 @@ def test_bits_of_subsets_defaults_and_reruns(lqrx, gpu_ok, prec):
     assert same_bits(f2["Einv"], sv.fac["Einv"]) and same_bits(f2["Pc"], sv.fac["Pc"])
 
 
+@pytest.mark.parametrize("prec", ["f64", "f32"])
+@pytest.mark.parametrize("shape", [(17, 5, 12, 3, True), (24, 18, 10, 3, False), (64, 32, 12, 2, False)], ids=sid)
+def test_rollout_of_the_resolved_policy_has_its_bits(lqrx, gpu_ok, shape, prec):
+    """S = 1: lqrx_dp_rollout of (K, the re-solve's own d) from the same x0, with no alpha, w or bounds, gives the
+    bits of the re-solve's X and U: the two kernels compute one and the same forward pass.  α = 1 multiplies exactly,
+    the clamp against ±∞ is the identity, c + 0 is c (the random c holds no −0), and the kernels' one-knot-ahead
+    policies, which differ at fp64 2×2 tiles, do not reach the bits."""
+    c = case(lqrx, shape, prec, 1)
+    r = c.run(outputs=("d", "X", "U"))
+    ro = lqrx.dp_rollout_device(c.sv.t, shape[2], c.sv.facd["K"], r["d"], dict(S=1, x0=c.rhs["x0"], outputs=("X", "U")))
+    for k in ("X", "U"):
+        assert same_bits(ro[k], r[k]), k
+
+
 # ---- guard zones ----
 def _filled(like, sizes):
     return {k: pattern_filled(like, sz) for k, sz in sizes.items()}

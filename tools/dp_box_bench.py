@@ -2,9 +2,9 @@
 """Same-run timing of the fused input-bounds kernel (lqrx_dp_resolve_box) against the loop a caller had to
 compose without it, and of its early stopping.
 
-  tools/dp_box_bench.py [--sets ti,tv] [--steps 5] [--warmup 1] [--S 64] [--iters 50] [--max-iter 500] [--eps 1e-6]
+  tools/dp_box_bench.py [--sets ti,tv] [--steps 5] [--warmup 1] [--S 64] [--shape 32,16,256] [--iters 50] [--max-iter 500] [--eps 1e-6]
 
-One process, one JSON line.  Per shape set (n = 32, m = 16, N = 256, fp64): the problem of
+One process, one JSON line.  Per shape set (n, m, N of --shape, fp64): the problem of
 tools/dp_rollout_bench.py, solved once by lqrx_dp_solve_cross with R + ρI (ρ = 1) and p_mode 1 and factored by
 lqrx_dp_factor; S instances per problem with q, r, qf, x0 ~ N(0, 1); bounds at ± half the peak of each problem's
 unconstrained controls (from the factors of R itself), the lower side of input 0 left open.  Every run starts
@@ -164,11 +164,14 @@ def main():
     ap.add_argument("--S", type=int, default=64)
     ap.add_argument("--batch-ti", type=int, default=1024)
     ap.add_argument("--batch-tv", type=int, default=256)
-    ap.add_argument("--N", type=int, default=256)
+    ap.add_argument("--shape", default="32,16,256", help="n,m,N of both shape sets")
+    ap.add_argument("--N", type=int, help="overrides the N of --shape")
     ap.add_argument("--iters", type=int, default=50, help="iterations of the fused / composed comparison")
     ap.add_argument("--max-iter", type=int, default=500)
     ap.add_argument("--eps", type=float, default=1e-6)
     args = ap.parse_args()
+    n, m, N = map(int, args.shape.split(","))
+    N = args.N or N
     import torch
     import lqrx
 
@@ -181,7 +184,7 @@ def main():
                device=torch.cuda.get_device_name(dev), library=lqrx._lib.build_info(), sets=[])
     for s in args.sets.split(","):
         tv = s == "tv"
-        out["sets"].append(run_set(lqrx, torch, dev, stream, 32, 16, args.N, args.batch_tv if tv else args.batch_ti,
+        out["sets"].append(run_set(lqrx, torch, dev, stream, n, m, N, args.batch_tv if tv else args.batch_ti,
                                    args.S, tv, args.seed, args.steps, args.warmup, args.iters, args.max_iter, args.eps))
         torch.cuda.empty_cache()
     print(json.dumps(out))

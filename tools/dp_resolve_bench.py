@@ -2,9 +2,9 @@
 """Same-run timing of factor + re-solve (lqrx_dp_factor, lqrx_dp_resolve) against what a caller had to
 do without them: lqrx_dp_solve_cross on the problem replicated to batch·S trajectories.
 
-  tools/dp_resolve_bench.py [--sets ti,tv] [--steps 5] [--warmup 1] [--S 64]
+  tools/dp_resolve_bench.py [--sets ti,tv] [--steps 5] [--warmup 1] [--S 64] [--shape 32,16,256]
 
-One process, one JSON line.  Per shape set (n = 32, m = 16, N = 256, fp64): the problem of
+One process, one JSON line.  Per shape set (n, m, N of --shape, fp64): the problem of
 tools/dp_rollout_bench.py, solved once by lqrx_dp_solve_cross with p_mode 1 for K and every P_k; S
 right-hand sides per problem with q, r, qf, x0 ~ N(0, 1) (q, r per knot in the time-varying set).
 Variants, alternated in every round and timed with device events: "factor" (lqrx_dp_factor alone),
@@ -126,8 +126,10 @@ def main():
     ap.add_argument("--S", type=int, default=64)
     ap.add_argument("--batch-ti", type=int, default=1024)
     ap.add_argument("--batch-tv", type=int, default=256)
+    ap.add_argument("--shape", default="32,16,256", help="n,m,N of both shape sets")
     ap.add_argument("--no-replicated", action="store_true", help="time the factor and the re-solve variants alone")
     args = ap.parse_args()
+    n, m, N = map(int, args.shape.split(","))
     import torch
     import lqrx
 
@@ -140,7 +142,7 @@ def main():
                device=torch.cuda.get_device_name(dev), library=lqrx._lib.build_info(), sets=[])
     for s in args.sets.split(","):
         tv = s == "tv"
-        out["sets"].append(run_set(lqrx, torch, dev, stream, 32, 16, 256, args.batch_tv if tv else args.batch_ti,
+        out["sets"].append(run_set(lqrx, torch, dev, stream, n, m, N, args.batch_tv if tv else args.batch_ti,
                                    args.S, tv, args.seed, args.steps, args.warmup, not args.no_replicated))
         torch.cuda.empty_cache()
     print(json.dumps(out))

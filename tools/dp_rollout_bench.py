@@ -2,9 +2,9 @@
 """Same-run timing of the scenario rollout (lqrx_dp_rollout) against what a caller had to do without
 it: lqrx_dp_solve_cross on the problem replicated to batch·S trajectories.
 
-  tools/dp_rollout_bench.py [--sets ti,tv] [--steps 5] [--warmup 1] [--S 64]
+  tools/dp_rollout_bench.py [--sets ti,tv] [--steps 5] [--warmup 1] [--S 64] [--shape 32,16,256]
 
-One process, one JSON line.  Per shape set (n = 32, m = 16, N = 256, fp64): the problem of
+One process, one JSON line.  Per shape set (n, m, N of --shape, fp64): the problem of
 tools/dp_kinds_bench.py (library generator, q, r, qf, c ~ N(0, 1), a cross term that keeps every
 problem strictly convex), solved once by lqrx_dp_solve_cross for the policy (K, d); S scenarios per
 problem with x0 ~ N(0, 1), α ~ U[0, 1], w ~ 0.1·N(0, 1) and bounds at ±1.5 × the mean |u| per problem
@@ -139,8 +139,10 @@ def main():
     ap.add_argument("--S", type=int, default=64)
     ap.add_argument("--batch-ti", type=int, default=1024)
     ap.add_argument("--batch-tv", type=int, default=256)
+    ap.add_argument("--shape", default="32,16,256", help="n,m,N of both shape sets")
     ap.add_argument("--no-replicated", action="store_true", help="time the rollout variants alone")
     args = ap.parse_args()
+    n, m, N = map(int, args.shape.split(","))
     import torch
     import lqrx
 
@@ -153,7 +155,7 @@ def main():
                device=torch.cuda.get_device_name(dev), library=lqrx._lib.build_info(), sets=[])
     for s in args.sets.split(","):
         tv = s == "tv"
-        out["sets"].append(run_set(lqrx, torch, dev, stream, 32, 16, 256, args.batch_tv if tv else args.batch_ti,
+        out["sets"].append(run_set(lqrx, torch, dev, stream, n, m, N, args.batch_tv if tv else args.batch_ti,
                                    args.S, tv, args.seed, args.steps, args.warmup, not args.no_replicated))
         torch.cuda.empty_cache()
     print(json.dumps(out))

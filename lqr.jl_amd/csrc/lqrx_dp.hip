@@ -227,6 +227,45 @@ template <typename T, int NT, int MT, int KT = NT> struct PnShadow {
     }
 };
 
+// VAR_DIAG's shadow: A₂ = [Σ | A₂₂] with Σ diagonal, so the product's tiles (i, j), i < MT, are row
+// scalings that the knot forms itself; what is left for the chain's shadow is A₂₂ᵀ·PA, the lower tiles
+// of rows MT … NT − 1 (At holds A₂₂'s tiles alone), in mma_tn_lower's order, cut into the same NCH chunks
+template <typename T, int NT, int MT, int KT> struct PnShadowDiag {
+    using acc = typename Tile<T>::acc;
+    static constexpr int NCH = 4 * MT + 2;
+    static constexpr int ROW = (NT * (NT + 1) - MT * (MT + 1)) / 2, TOT = KT * 4 * ROW;   // per k-slice, in all
+    static constexpr int beg(int c) { return c * TOT / NCH; }
+    acc (&Pn)[NT][NT];
+    const acc (&At)[KT][NT - MT];
+    const acc (&PA)[KT][NT];
+    template <int B, int E> __device__ __forceinline__ void range() const
+    {
+        int idx = 0;
+#pragma unroll
+        for (int k = 0; k < KT; ++k)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int i = MT; i < NT; ++i)
+#pragma unroll
+                    for (int j = 0; j <= i; ++j, ++idx)
+                        if (idx >= beg(B) && idx < beg(E))
+                            Pn[i][j] = Tile<T>::mma(At[k][i - MT][r], PA[k][j][r], Pn[i][j]);
+    }
+    template <int C> __device__ __forceinline__ void chunk() const
+    {
+        __builtin_amdgcn_sched_barrier(0);
+        range<C, C + 1>();
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    __device__ __forceinline__ void rest(int done) const
+    {
+        if (done < 1) range<0, 1>();
+        if (done < 4 * MT + 1) range<1, 4 * MT + 1>();
+        if (done < NCH) range<4 * MT + 1, NCH>();
+    }
+};
+
 // k-slice S (k-tile S / 4, register S % 4) of mma_tn(X, X, R) and the slices after it, chunk
 // 1 + S behind each
 template <typename T, int MT, int S, typename F>
@@ -334,6 +373,7 @@ template <typename T, int NT, int MT> struct DpCfg {
     static constexpr int AUGC = 2 * MP * CS + 64 + MP, KTI = NP * CS;
     static constexpr int WORK_CANON = imax(imax(AUGC, ROLL), imax(SYM, KTI));
     static constexpr int LDS_CANON = WORK_CANON + MP * CS;   // + the Sᵀ image (read once per knot), behind the work area
+    static constexpr int LDS_DIAG = LDS_CANON + MP;          // VAR_DIAG: + σ (read twice per knot), behind Sᵀ
 };
 
 // Forward rollout  dynamic_programming.jl:66-70 :  u_k = −K_k x_k ; x_{k+1} = A x_k + B u_k.
@@ -736,9 +776,15 @@ __device__ __forceinline__ void dp_rollout_full(const DpArgs &a, int64_t b, T *l
 //                start) and P̃₂₂A₂; Q′ + A₂ᵀ(P̃₂₂A₂) is PnShadow's shorter product; the ABI's gain is
 //                K = S·K_v·Tᵀ + C, C = S·A₁·Tᵀ of the workspace the accumulators' start, loaded every
 //                knot (cache-resident) behind −GᵀK_v.  80 MFMAs per knot where VAR_CANON has 108.
+//   VAR_DIAG   : on top of VAR_CANON | VAR_PREFB, n = 2m, for the trajectories the set-up flags 3: it has
+//                rotated the basis by the SVD of A₂'s left block, x̃ → diag(U₁, U₂)ᵀx̃, ũ → U₁ᵀũ (B̃ stays
+//                [I; 0]; T·diag(U₁, U₂), S·U₁ stand where T, S stood), so that A₂ = [Σ | A₂₂] with Σ
+//                diagonal.  Only A₂₂'s tiles are held, σ lives in LDS; column tile 0 of [P̃₁₂; P̃₂₂]·A₂ is
+//                a column scaling of P̃'s tiles (M′ the addend for G), tile (0, 0) of A₂ᵀ(P̃₂₂A₂) a row
+//                scaling of PA's: 12 v_fma_f64 where VAR_PREFB has 12 MFMAs.  68 MFMAs per knot.
 enum : int { VAR_NOSOLVE = 2, VAR_NOROLL = 4, VAR_NOKSTORE = 8, VAR_SWEEPONLY = 16, VAR_TV = 32,
              VAR_LIN = 64, VAR_AFF = 128, VAR_CROSS = 256, VAR_VALUE = 512, VAR_CANON = 1024, VAR_MASK = 2048,
-             VAR_PREFB = 4096 };
+             VAR_PREFB = 4096, VAR_DIAG = 8192 };
 
 // Vector products with register tiles (VAR_LIN).  A vector v is read from its LDS image in
 // "row layout" (lane l, slot [i][r] = v[16i + Tile::row(l, r)], the rows a C-layout tile's
@@ -796,11 +842,14 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
     static_assert(!MASK || (!TV && !LIN), "VAR_MASK: the plain time-invariant kernel");
     constexpr bool PREFB = (VAR & VAR_PREFB) != 0;
     static_assert(!PREFB || (CANON && MT < NT), "VAR_PREFB extends VAR_CANON, m < n");
+    constexpr bool DIAG = (VAR & VAR_DIAG) != 0;
+    static_assert(!DIAG || (PREFB && NT == 2 * MT), "VAR_DIAG extends VAR_PREFB, n = 2m");
     constexpr int AK = PREFB ? NT - MT : NT;                    // A's row tiles in registers (VAR_PREFB: A₂ alone)
+    constexpr int AJ = DIAG ? NT - MT : NT;                     // and its column tiles (VAR_DIAG: A₂₂ alone)
     // Q + AᵀPA in the shadow of the Newton–Schulz chain (PnShadow): time-invariant A only
     constexpr bool SHADOW = !TV && (VAR & (VAR_NOSOLVE | VAR_SWEEPONLY)) == 0;
     constexpr int NP = C::NP;
-    __shared__ T lds[CANON ? C::LDS_CANON : C::LDS_ELEMS];
+    __shared__ T lds[DIAG ? C::LDS_DIAG : CANON ? C::LDS_CANON : C::LDS_ELEMS];
     // p (NP), then w / d (MP); time-invariant q (NP), r (MP) images after them; VAR_AFF: one more
     // NP slot, the time-invariant c image
     constexpr int CIMG = TV ? NP + MP : 2 * (NP + MP);
@@ -817,7 +866,7 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
     // VAR_CANON / VAR_MASK: the set-up's verdict on this trajectory (wave-uniform), each kernel of
     // the launch takes the trajectories of its own flag value
     if constexpr (CANON || MASK) {
-        if (DpCanonWs<T, NT, MT>::flags(a.M)[b] != (PREFB ? 2 : CANON ? 1 : 0)) return;
+        if (DpCanonWs<T, NT, MT>::flags(a.M)[b] != (DIAG ? 3 : PREFB ? 2 : CANON ? 1 : 0)) return;
     }
     const int n = a.n, m = a.m, N = a.N;
     const size_t nn = (size_t)n * n, nm = (size_t)n * m, mm = (size_t)m * m;
@@ -836,7 +885,7 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
     const size_t sM = (CROSS && kQR > 1) ? nm : 0;
     const T *Mb = CROSS ? (const T *)a.M + b * nm * kQR : nullptr;
 
-    acc At[AK][NT], Bt[CANON ? 1 : NT][MT], Rt[MT][MT], P[NT][NT];
+    acc At[AK][AJ], Bt[CANON ? 1 : NT][MT], Rt[MT][MT], P[NT][NT];
     acc Tt[CANON ? NT : 1][CANON ? NT : 1];                     // VAR_CANON: Tᵀ
     acc Mp[PREFB ? MT : 1][PREFB ? NT : 1];                     // VAR_PREFB: M′
     const T *Cg = nullptr;                                      // VAR_PREFB: C of the workspace
@@ -846,7 +895,12 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
         const T *wsb = W::block(a.M, a.batch, b);
         Qg = wsb + W::oQ;                                       // VAR_PREFB: the set-up wrote Q′ there
         if constexpr (PREFB) {
-            tiles_load<T, AK, NT, true>(At, wsb + W::oA + MP, n - m, n, n, lane, false);   // rows m … of Ã
+            if constexpr (DIAG) {
+                // rows and columns m … of Ã alone; σ to its image (the barrier behind the Q image covers it)
+                tiles_load<T, AK, AJ, true>(At, wsb + W::oA + MP + (size_t)MP * n, n - m, n - m, n, lane, false);
+                if (lane < MP) lds[C::LDS_CANON + lane] = W::sigma(a.M, a.batch, b)[lane];
+            } else
+                tiles_load<T, AK, NT, true>(At, wsb + W::oA + MP, n - m, n, n, lane, false);   // rows m … of Ã
             tiles_load<T, MT, NT, true>(Mp, wsb + W::oMp, m, n, m, lane, false);
             Cg = wsb + W::oC;
         } else
@@ -1030,17 +1084,46 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
 #pragma unroll
                 for (int j = 0; j < NT; ++j) G[i][j] = Mp[i][j];
             tiles_zero<T, AK, NT>(PA);
+            if constexpr (DIAG) {
+                // A₂ = [Σ | A₂₂]: column tiles 0 … are P̃'s tiles (m …, ·) with their columns scaled by σ — P̃ is
+                // exactly symmetric, so (m + j, i)ᵀ is the tile (i, m + j) as it stands —, the others the
+                // product with A₂₂ in the order above
+                int ls = lane;                                     // laundered: the image offset is formed per knot
+                asm volatile("" : "+v"(ls));
 #pragma unroll
-            for (int kk = 0; kk < AK; ++kk)
+                for (int j = 0; j < MT; ++j) {
+                    const T sc = lds[C::LDS_CANON + 16 * j + tcol(ls)];
 #pragma unroll
-                for (int r = 0; r < 4; ++r)
+                    for (int i = 0; i < NT; ++i) {
+                        acc &D = i < MT ? G[i][j] : PA[i < MT ? 0 : i - MT][j];
 #pragma unroll
-                    for (int i = 0; i < NT; ++i)
+                        for (int r = 0; r < 4; ++r) D[r] = fma(P[i][MT + j][r], sc, D[r]);
+                    }
+                }
 #pragma unroll
-                        for (int j = 0; j < NT; ++j) {
-                            acc &D = i < MT ? G[i][j] : PA[i < MT ? 0 : i - MT][j];
-                            D = Tile<T>::mma(P[MT + kk][i][r], At[kk][j][r], D);
-                        }
+                for (int kk = 0; kk < AK; ++kk)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+#pragma unroll
+                        for (int i = 0; i < NT; ++i)
+#pragma unroll
+                            for (int j = MT; j < NT; ++j) {
+                                acc &D = i < MT ? G[i][j] : PA[i < MT ? 0 : i - MT][j];
+                                D = Tile<T>::mma(P[MT + kk][i][r], At[kk][j - MT][r], D);
+                            }
+            } else {
+#pragma unroll
+                for (int kk = 0; kk < AK; ++kk)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+#pragma unroll
+                        for (int i = 0; i < NT; ++i)
+#pragma unroll
+                            for (int j = 0; j < NT; ++j) {
+                                acc &D = i < MT ? G[i][j] : PA[i < MT ? 0 : i - MT][j];
+                                D = Tile<T>::mma(P[MT + kk][i][r], At[kk][j][r], D);
+                            }
+            }
         } else {
             tiles_zero<T, AK, NT>(PA);
             mma_tn<T, NT, NT, NT>(PA, P, At);                      // :40 PA = P A
@@ -1085,7 +1168,8 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
         // :51 Q + A'PA (lower): independent of the solve.  Time-invariant A: issued in chunks in
         // the shadow of the Newton–Schulz chain below (PnShadow); time-varying: here, before
         // A_k leaves the tiles.
-        const PnShadow<T, NT, MT, AK> pn_shadow{Pn, At, PA};        // VAR_PREFB: Q′ + A₂ᵀ(P̃₂₂A₂)
+        using Shadow = std::conditional_t<DIAG, PnShadowDiag<T, NT, MT, AK>, PnShadow<T, NT, MT, AK>>;
+        const Shadow pn_shadow{Pn, At, PA};                         // VAR_PREFB: Q′ + A₂ᵀ(P̃₂₂A₂)
         int pn_done = 0;
         if constexpr (!SHADOW) mma_tn_lower<T, AK, NT>(Pn, At, PA);
         // linear terms, first half (time-varying: before A_k, B_k leave the tiles; time-
@@ -1182,6 +1266,21 @@ __global__ __launch_bounds__(64, WAVES) void dp_riccati_kernel(const DpArgs a)
             }
             tiles_zero<T, MT, NT>(Kt);
             mma_tn<T, MT, MT, NT>(Kt, Xi, G);                          // K = XᵀG = E⁻¹G
+            if constexpr (DIAG) {
+                // tiles (i, j), i < m/16, of A₂ᵀ(P̃₂₂A₂): PA's tiles with their rows scaled by σ, here, behind
+                // the solve (ahead of the exact sweep σ's registers were live across it: 4 VGPRs spilled); the
+                // other tiles are the Newton–Schulz chain's shadow (PnShadowDiag)
+                int ls = lane;                                         // laundered: the image offsets are formed per knot
+                asm volatile("" : "+v"(ls));
+#pragma unroll
+                for (int i = 0; i < MT; ++i)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const T sr = lds[C::LDS_CANON + 16 * i + Tile<T>::row(ls, r)];
+#pragma unroll
+                        for (int j = 0; j <= i; ++j) Pn[i][j][r] = fma(sr, PA[i][j][r], Pn[i][j][r]);
+                    }
+            }
             // VAR_CANON: K̃ to its LDS image here; the ABI's gain is formed from it behind −GᵀK, below
             if constexpr (CANON) tiles_to_lds<T, MT, NT>(Kt, lds, CS, lane);
             else if constexpr ((VAR & VAR_NOKSTORE) == 0)

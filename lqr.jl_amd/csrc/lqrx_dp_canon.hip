@@ -13,6 +13,10 @@
 // with the deadbeat pre-feedback (VAR_PREFB, lqrx_dp_prefb.hip), where κ∞(B₁) is also under
 // DP_PREFB_KAPPA_F64: for those the kernel writes Q′ = Q̃ + A₁ᵀR̃A₁ in Q̃'s place and, behind Sᵀ,
 // M′ = −R̃A₁ and C = S·A₁·Tᵀ (A₁ the first m rows of Ã), 36 MFMAs more per trajectory.
+// 3, the pre-feedback form in the basis where A₂₁, the lower-left block of Ã, is diagonal (VAR_DIAG,
+// lqrx_dp_diag.hip; n = 2m, κ∞(B₁) also under DP_DIAG_KAPPA_F64): x̃ → diag(U₁, U₂)ᵀx̃, ũ → U₁ᵀũ from the
+// SVD A₂₁ = U₂ΣU₁ᵀ by a one-sided Jacobi in the wave (dg_jacobi) keep B̃ = [I; 0]; T·diag(U₁, U₂) and S·U₁
+// then stand where T and S stand above, and σ is written behind the last trajectory's block.
 //
 // The reflectors run on the augmented matrix [B | I] (n × (m + n)), one column per lane in
 // registers: after the m steps the first m lanes hold B₁ and the other n hold Tᵀ.  Reflector j's
@@ -30,8 +34,100 @@
 
 namespace lqrx {
 
+// x of lane l ^ 1 / l ^ 2 (DPP quad_perm: no LDS traffic), for the sums over a quad of lanes
+template <int CTRL> __device__ __forceinline__ double quad_swap(double v)
+{
+    const long long x = __double_as_longlong(v);
+    const int lo = __builtin_amdgcn_update_dpp(0, (int)(x & 0xffffffffll), CTRL, 0xf, 0xf, true);
+    const int hi = __builtin_amdgcn_update_dpp(0, (int)(x >> 32), CTRL, 0xf, 0xf, true);
+    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
+__device__ __forceinline__ double quad_sum(double v)
+{
+    v += quad_swap<0xB1>(v);            // quad_perm:[1,0,3,2]
+    return v + quad_swap<0x4E>(v);      // quad_perm:[2,3,0,1]
+}
+
+// One-sided (Hestenes) Jacobi on the 16 columns of W (16×16, in `img` at column stride CS), VAR_DIAG's
+// set-up: on return the columns of W·V are orthogonal, u2 holds W·V·diag(1/σ) and u1 holds V, as images
+// at the same stride.  Lane 4j + c holds rows 4c … 4c + 3 of column j of W and of V.  A sweep is the 15
+// steps of a round-robin tournament, 8 disjoint pairs each: column 15 meets column t, the others pair up
+// with i + j ≡ 2t (mod 15).  Both lanes of a pair fetch the other column (ds_bpermute), form the same
+// three dot products bit for bit, and rotate their own column by the tangent of their own view,
+// own ← c·(own − t·other): the two views differ by the sign of t alone (equal norms: by index).  A pair rotates while
+// (w_p·w_q)² > (tol·‖w_p‖‖w_q‖)².  The sweeps are a counted loop; the verdict — a sweep went by without a
+// rotation, and every σ inside [DP_DIAG_SIGMA_LO, DP_DIAG_SIGMA_HI], false for a NaN — is wave-uniform.
+__device__ __forceinline__ bool dg_jacobi(const double *img, double *u1, double *u2, int CS, int lane)
+{
+    const int j = lane >> 2, c = lane & 3;
+    double w[4], v[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        w[i] = img[4 * c + i + j * CS];
+        v[i] = (4 * c + i == j) ? 1.0 : 0.0;
+    }
+    constexpr double tol = DP_DIAG_ROT_EPS * 2.220446049250313e-16, tol2 = tol * tol;
+    bool conv = false;
+#pragma unroll 1
+    for (int sw = 0; sw < DP_DIAG_SWEEPS && !conv; ++sw) {
+        bool rot = false;
+#pragma unroll 1
+        for (int t = 0; t < 15; ++t) {
+            int k = (2 * t - j + 15) % 15;
+            k = j == 15 ? t : (k == j ? 15 : k);
+            const int src = 4 * k + c;
+            double wo[4], vo[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                wo[i] = __shfl(w[i], src);
+                vo[i] = __shfl(v[i], src);
+            }
+            double aa = 0.0, bb = 0.0, gg = 0.0;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                aa = fma(w[i], w[i], aa);
+                bb = fma(wo[i], wo[i], bb);
+                gg = fma(w[i], wo[i], gg);
+            }
+            aa = quad_sum(aa);
+            bb = quad_sum(bb);
+            gg = quad_sum(gg);
+            const bool r = gg * gg > tol2 * (aa * bb);
+            rot = rot || r;
+            // the rotation, division-free: with d = ‖other‖² − ‖own‖², h = √(d² + (2γ)²), D = |d| + h the tangent is
+            // t = sign(d)·2γ/D and c = D/√(D² + (2γ)²), so own ← q·(D·own − sign(d)·2γ·other), q = 1/√(D² + (2γ)²);
+            // d = 0: the lower column takes +1.  None: c = 1, c·t = 0
+            const double d = bb - aa, g2 = 2.0 * gg;
+            const double h2 = fma(d, d, g2 * g2);
+            const double D = fabs(d) + h2 * rsqrt_nr(h2);
+            const double q = rsqrt_nr(fma(D, D, g2 * g2));
+            const bool pos = d != 0.0 ? d > 0.0 : j < k;
+            const double cs = r ? D * q : 1.0, ct = r ? (pos ? g2 * q : -(g2 * q)) : 0.0;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                w[i] = fma(-ct, wo[i], cs * w[i]);
+                v[i] = fma(-ct, vo[i], cs * v[i]);
+            }
+        }
+        conv = !__any(rot);
+    }
+    double aa = 0.0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) aa = fma(w[i], w[i], aa);
+    const double sg = sqrt(quad_sum(aa));
+    const bool ok = conv && __all(sg >= DP_DIAG_SIGMA_LO && sg <= DP_DIAG_SIGMA_HI);
+    const double inv = 1.0 / sg;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        u2[4 * c + i + j * CS] = w[i] * inv;
+        u1[4 * c + i + j * CS] = v[i];
+    }
+    return ok;
+}
+
 template <typename T, int NT, int MT>
-__global__ __launch_bounds__(64) void dp_canon_prep_kernel(const DpArgs a, void *wsv, T kappa_max, T kappa_pf)
+__global__ __launch_bounds__(64) void dp_canon_prep_kernel(const DpArgs a, void *wsv, T kappa_max, T kappa_pf,
+                                                           T kappa_dg)
 {
     using acc = typename Tile<T>::acc;
     using W = DpCanonWs<T, NT, MT>;
@@ -135,6 +231,84 @@ __global__ __launch_bounds__(64) void dp_canon_prep_kernel(const DpArgs a, void 
                 Tn[i][j][r] = timg[(j * 16 + tcol(lane)) + (i * 16 + Tile<T>::row(lane, r)) * TS];
     tiles_from_lds<T, MT, MT>(Sn, simg, SS, lane);
     __syncthreads();                                                    // timg is free from here
+    // The diagonal-A₂₁ tier (VAR_DIAG, flag 3; wave-uniform branch), for a pre-feedback trajectory with κ∞(B₁)
+    // also under kappa_dg: with the SVD A₂₁ = U₂ΣU₁ᵀ of Ã's lower-left block, T′ = T·diag(U₁, U₂) and S′ = S·U₁
+    // keep B̃ = [I; 0] and make that block Σ.  Admitted when the Jacobi's verdict is good and the block as the
+    // congruence below will form it from T′ — the same products in the same order, so the same bits — has a
+    // diagonal σ above DP_DIAG_OFF_EPS·ε·σ_max and nothing beside it above that bound (what the solve kernel then
+    // drops is a backward error in A of that size).  T′ and S′ then stand where T and S stood in everything below.
+    // Otherwise nothing here has touched T, S or the workspace: flag 2, the parent's bytes.
+    if constexpr (NT == 2 && MT == 1) {
+        if (pf && kappa <= kappa_dg) {
+            acc Ttt[NT][NT], Xa[NT][NT], Yc[NT][1], Tc[NT][1], Zc[1][1];
+            tiles_from_lds<T, NT, NT>(Ttt, timg, TS, lane);             // Tᵀ's tiles, as they stand in the image
+            tiles_load<T, NT, NT, true>(Xa, (const T *)a.A + b * nn, NP, NP, NP, lane, false);
+            // Ã₂₁ = (AᵀT₂)ᵀT₁
+            auto lower_left = [&](const acc (&Tm)[NT][NT]) {
+#pragma unroll
+                for (int k = 0; k < NT; ++k) Tc[k][0] = Tm[k][1];
+                tiles_zero<T, NT, 1>(Yc);
+                mma_tn<T, NT, NT, 1>(Yc, Xa, Tc);
+#pragma unroll
+                for (int k = 0; k < NT; ++k) Tc[k][0] = Tm[k][0];
+                tiles_zero<T, 1, 1>(Zc);
+                mma_tn<T, NT, 1, 1>(Zc, Yc, Tc);
+            };
+            lower_left(Tn);
+            __syncthreads();
+            tiles_to_lds<T, 1, 1>(Zc, bimg, SS, lane);                  // B₁'s image is dead: W, then U₂
+            __syncthreads();
+            const bool jac = dg_jacobi(bimg, timg, bimg, SS, lane);     // U₁ to the head of the Tᵀ image
+            __syncthreads();
+            if (jac) {
+                acc U[NT][1][1], Tp[NT][NT], Stt[1][1], Sp[1][1];
+                tiles_from_lds<T, 1, 1>(U[0], timg, SS, lane);
+                tiles_from_lds<T, 1, 1>(U[1], bimg, SS, lane);
+                // T′ = T·diag(U₁, U₂): tile (i, j) = (Tᵀ's tile (j, i))ᵀ·U_j;  S′ = (Sᵀ)ᵀ·U₁
+#pragma unroll
+                for (int i = 0; i < NT; ++i)
+#pragma unroll
+                    for (int j = 0; j < NT; ++j) {
+                        Tp[i][j] = acc{0, 0, 0, 0};
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) Tp[i][j] = Tile<T>::mma(Ttt[j][i][r], U[j][0][0][r], Tp[i][j]);
+                    }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) Stt[0][0][r] = simg[tcol(lane) + Tile<T>::row(lane, r) * SS];
+                tiles_zero<T, 1, 1>(Sp);
+                mma_tn<T, 1, 1, 1>(Sp, Stt, U[0]);
+                lower_left(Tp);
+                // σ: the block's diagonal (lane l, register r holds (row(l, r), l & 15))
+                T dmax = (T)0;
+                bool good = true;
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (Tile<T>::row(lane, r) == tcol(lane)) {
+                        dmax = Zc[0][0][r];
+                        good = good && Zc[0][0][r] > (T)0;                  // false for a NaN
+                    }
+                // σ_min above the bound too: under it σ is no larger than what is dropped beside it, its sign is
+                // rounding's, and A₂₁ is rank-deficient to working precision
+                const T bound = (T)(DP_DIAG_OFF_EPS * 2.220446049250313e-16) * wave_max(dmax);
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    good = good && (Tile<T>::row(lane, r) != tcol(lane) ? fabs(Zc[0][0][r]) <= bound : Zc[0][0][r] > bound);
+                if (__all(good)) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (Tile<T>::row(lane, r) == tcol(lane)) W::sigma(wsv, a.batch, b)[tcol(lane)] = Zc[0][0][r];
+#pragma unroll
+                    for (int i = 0; i < NT; ++i)
+#pragma unroll
+                        for (int j = 0; j < NT; ++j) Tn[i][j] = Tp[i][j];
+                    Sn[0][0] = Sp[0][0];
+                    tiles_to_lds<T, 1, 1>(Sp, simg, SS, lane);          // the pre-feedback data reads S from its image
+                    if (lane == 0) *flag = 3;
+                }
+            }
+            __syncthreads();
+        }
+    }
     // Tᵀ and Sᵀ: T's and S's tiles stored transposed
 #pragma unroll
     for (int i = 0; i < NT; ++i)
@@ -230,10 +404,10 @@ __global__ __launch_bounds__(64) void dp_canon_prep_kernel(const DpArgs a, void 
     tiles_store<T, NT, NT, true>(Z, ws + W::oQf, NP, NP, NP, lane);
 }
 
-// The canonical-form solve: the set-up fills a pool workspace and sorts the trajectories into three
-// tiers; the VAR_PREFB kernel solves those flagged 2, the VAR_CANON kernel those flagged 1, the
-// generic kernel behind them (VAR_MASK) the ones the set-up did not admit — over the same grid, each
-// an empty launch (16 µs) when it has none.  Stream-ordered throughout: no host synchronisation.  Where
+// The canonical-form solve: the set-up fills a pool workspace and sorts the trajectories into four
+// tiers; the VAR_DIAG kernel solves those flagged 3, the VAR_PREFB kernel those flagged 2, the VAR_CANON
+// kernel those flagged 1, the generic kernel behind them (VAR_MASK) the ones the set-up did not admit —
+// over the same grid, each an empty launch (16 µs) when it has none.  Stream-ordered throughout: no host synchronisation.  Where
 // the pool cannot give the workspace (44 KB per trajectory) nothing is launched and *ran is false.
 hipError_t dp_canon_launch(const DpArgs &a_in, hipStream_t s, bool *ran)
 {
@@ -249,11 +423,14 @@ hipError_t dp_canon_launch(const DpArgs &a_in, hipStream_t s, bool *ran)
     a.M = ws;
     dim3 grid((unsigned)a.batch), block(64);
     // LQRX_DP_PREFB=0 in the environment (read once): no trajectory gets flag 2 — κ∞ ≥ 1 is above a
-    // zero bound — so the pre-feedback candidates go to the VAR_CANON kernel
+    // zero bound — so the pre-feedback candidates go to the VAR_CANON kernel.  LQRX_DP_DIAG=0 likewise: no
+    // flag 3, the diagonal-A₂₁ candidates go to the pre-feedback kernel; LQRX_DP_PREFB=0 switches both off
     static const bool prefb = [] { const char *e = std::getenv("LQRX_DP_PREFB"); return !(e && *e == '0'); }();
+    static const bool diag = [] { const char *e = std::getenv("LQRX_DP_DIAG"); return !(e && *e == '0'); }();
     hipLaunchKernelGGL((dp_canon_prep_kernel<double, 2, 1>), grid, block, 0, s, a, ws, DP_CANON_KAPPA_F64,
-                       prefb ? DP_PREFB_KAPPA_F64 : 0.0);
+                       prefb ? DP_PREFB_KAPPA_F64 : 0.0, prefb && diag ? DP_DIAG_KAPPA_F64 : 0.0);
     hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = dp_diag_launch(a, s);
     if (e == hipSuccess) e = dp_prefb_launch(a, s);
     if (e == hipSuccess) {
         hipLaunchKernelGGL((dp_riccati_kernel<double, 2, 1, 2, VAR_CANON, true>), grid, block, 0, s, a);

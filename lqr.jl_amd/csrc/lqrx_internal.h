@@ -85,10 +85,13 @@ hipError_t dp_value_cost_launch(const DpArgs &a, void *J, hipStream_t s);
 hipError_t batch_transpose(const void *in, void *out, int64_t rows, int64_t cols, int elem_bytes, hipStream_t s);
 bool dp_supported(int dtype, int n, int m, bool tv);
 // Workspace of a canonical-form solve (lqrx_dp_canon.hip writes it, dp_riccati_kernel's VAR_CANON /
-// VAR_MASK / VAR_PREFB variants read it): one int32 flag per trajectory (2: canonical with the
-// pre-feedback, 1: canonical, 0: generic), then per trajectory Ã, Q̃, Q̃f, Tᵀ (n² each), R̃, Sᵀ (m² each),
-// column-major.  A flag-2 trajectory has Q′ in Q̃'s place and behind Sᵀ M′ (m×n, column-major) and C
-// (m×n, as the lanes hold its tiles: tile, lane, register).  It reaches those kernels in
+// VAR_MASK / VAR_PREFB / VAR_DIAG variants read it): one int32 flag per trajectory (3: canonical with the
+// pre-feedback in the basis where A₂₁ is diagonal, 2: canonical with the pre-feedback, 1: canonical,
+// 0: generic), then per trajectory Ã, Q̃, Q̃f, Tᵀ (n² each), R̃, Sᵀ (m² each), column-major.  A flag-2 or
+// flag-3 trajectory has Q′ in Q̃'s place and behind Sᵀ M′ (m×n, column-major) and C (m×n, as the lanes
+// hold its tiles: tile, lane, register).  Behind the last trajectory's block, m doubles per trajectory:
+// σ, A₂₁'s diagonal, of a flag-3 trajectory (a region of its own, so that the blocks keep their stride
+// and the kernels that read them their code).  It reaches those kernels in
 // DpArgs::M — a plain solve has no cross term, so M is otherwise unread there — and DpArgs, with it
 // every other kernel's argument block, stays as it is.
 template <typename T, int NT, int MT> struct DpCanonWs {
@@ -97,7 +100,8 @@ template <typename T, int NT, int MT> struct DpCanonWs {
     static constexpr size_t oMp = 4 * nn + 2 * mm, oC = oMp + nm;
     static constexpr size_t per = 4 * nn + 2 * mm + 2 * nm;            // elements per trajectory
     static __host__ __device__ size_t flag_bytes(int64_t batch) { return ((size_t)batch * 4 + 255) / 256 * 256; }
-    static __host__ __device__ size_t bytes(int64_t batch) { return flag_bytes(batch) + (size_t)batch * per * sizeof(T); }
+    static __host__ __device__ size_t sigma_off(int64_t batch) { return flag_bytes(batch) + (size_t)batch * per * sizeof(T); }
+    static __host__ __device__ size_t bytes(int64_t batch) { return sigma_off(batch) + (size_t)batch * 16 * MT * sizeof(T); }
     static __host__ __device__ int32_t *flags(void *ws) { return (int32_t *)ws; }
     static __host__ __device__ const int32_t *flags(const void *ws) { return (const int32_t *)ws; }
     static __host__ __device__ T *block(void *ws, int64_t batch, int64_t b)
@@ -108,9 +112,17 @@ template <typename T, int NT, int MT> struct DpCanonWs {
     {
         return (const T *)((const char *)ws + flag_bytes(batch)) + (size_t)b * per;
     }
+    static __host__ __device__ T *sigma(void *ws, int64_t batch, int64_t b)
+    {
+        return (T *)((char *)ws + sigma_off(batch)) + (size_t)b * 16 * MT;
+    }
+    static __host__ __device__ const T *sigma(const void *ws, int64_t batch, int64_t b)
+    {
+        return (const T *)((const char *)ws + sigma_off(batch)) + (size_t)b * 16 * MT;
+    }
 };
 // the canonical-form solve of a plain time-invariant fp64 n = 32, m = 16, P_1-only call (lqrx_dp_canon.hip):
-// set-up, VAR_PREFB kernel, VAR_CANON kernel, VAR_MASK kernel.  *ran = false (and nothing launched,
+// set-up, VAR_DIAG kernel, VAR_PREFB kernel, VAR_CANON kernel, VAR_MASK kernel.  *ran = false (and nothing launched,
 // hipSuccess) when the pool cannot give the workspace: the caller then takes the generic launch.
 hipError_t dp_canon_launch(const DpArgs &a, hipStream_t s, bool *ran);
 // the VAR_CANON | VAR_PREFB instantiation's launch (lqrx_dp_prefb.hip, a module of its own), on the
@@ -124,6 +136,19 @@ constexpr double DP_CANON_KAPPA_F64 = 2.5e13;
 // R̃ = SᵀRS grows like κ(B₁)², so digits go in proportion.  A factor 4 under the point of the sweep of
 // tests/dp_canon_pf_truth.py where the modelled gain error first reaches 1e-11
 constexpr double DP_PREFB_KAPPA_F64 = 4.7e2;
+// the VAR_CANON | VAR_PREFB | VAR_DIAG instantiation's launch (lqrx_dp_diag.hip, a module of its own), likewise
+hipError_t dp_diag_launch(const DpArgs &a, hipStream_t s);
+// κ∞(B₁) bound of the diagonal-A₂₁ tier (VAR_DIAG): the rotation U₁ mixes Ẽ's graded basis, and the
+// Newton–Schulz acceptance on max |I − EX| then leaves more of the residual in the gain.  A factor 4 under
+// the point of the sweep of tests/dp_canon_dg_truth.py where the modelled gain error first reaches 1e-11
+// 
+constexpr double DP_DIAG_KAPPA_F64 = 1.4e2;
+// the set-up's one-sided Jacobi on A₂₁ (lqrx_dp_canon.hip): cap on sweeps, rotation threshold on
+// |w_p·w_q| / (‖w_p‖‖w_q‖) in units of ε, admission bound on the recomputed block's off-diagonal in units
+// of ε·σ_max (4n: two chained n-term products with orthogonal factors, ‖A‖₂ up to twice σ_max) and the
+// range of σ in which the threshold's products neither underflow nor overflow
+constexpr int DP_DIAG_SWEEPS = 12;
+constexpr double DP_DIAG_ROT_EPS = 16.0, DP_DIAG_OFF_EPS = 128.0, DP_DIAG_SIGMA_LO = 1e-60, DP_DIAG_SIGMA_HI = 1e60;
 // lane-per-trajectory kernel for n ≤ 4, m ≤ 4 (lqrx_dp_lane.hip)
 hipError_t dp_lane_launch(const DpArgs &a, int kind, hipStream_t s);
 bool dp_lane_supported(int n, int m);

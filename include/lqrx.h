@@ -595,6 +595,8 @@ int lqrx_dp_resolve_box_host(const lqrx_dp_desc *desc, const void *A, const void
  * Block structure (shared by the whole batch) = ConstraintBlocks (conblocks.jl:403-425):
  * knot k (0-based here) has n1[k] previous-dynamics rows D2, p[k] stage rows C, n2[k]
  * dynamics rows D1 and width w[k] (= n̄ + m for k < N-1, n̄ at the last knot).
+ * The four arrays are free per knot — only n1[0] = 0, n1[k] = n2[k-1] and n2[N-1] = 0 are
+ * required — and Y is data.
  * Packed per-trajectory inputs, each block column-major, concatenated over k:
  *   Y  (n1+p+n2)×w   Y = [D2; C; D1]   (ConstraintBlock.Y)
  *   y  p+n2          y = [c; d]        (ConstraintBlock.y)

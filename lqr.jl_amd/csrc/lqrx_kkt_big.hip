@@ -2909,7 +2909,7 @@ struct KbPlan {
     int nbt;                        // split: the Schur kernel's block grid (max R / 16)
     int mid0, mid1, midnt;          // split: knots [mid0, mid1) run on kb_factor_mid_kernel<midnt>
     bool fuse;                      // … or on kb_fuse_mid_kernel<midnt> (no Schur images there)
-    bool midfull;                   // fused: n2 of the run a multiple of 16 (whole row blocks)
+    bool midfull;                   // fused: n1 = n2 = 16·midnt at every knot of the run (whole row blocks)
     int nr0;                        // Schur runs over knots [0, mid0) (fused) or all runs
 };
 
@@ -3021,7 +3021,11 @@ bool kb_plan(const KktArgs &a, const int32_t *n1, const int32_t *p, const int32_
     // fused interior run: the Schur kernel covers [0, mid0) and [mid1, N) only, and the
     // interior knots get no image
     P.fuse = P.midnt > 0 && P.mid1 < a.N && kb_fuse_env() != 0;
-    P.midfull = P.fuse && n2[P.mid0] == 16 * P.midnt;
+    // FULL addresses whole 16-row blocks, D1 at row 16·midnt, at every knot the fused kernel streams
+    // (q1 over the run, q2 one knot on: n1[mid1] = n2[mid1 − 1]), so every knot of the run must be
+    // full — the run's bin only pads them alike (a ragged knot inside read D1 rows as D2 rows)
+    P.midfull = P.fuse;
+    for (int k = P.mid0; k < P.mid1 && P.midfull; ++k) P.midfull = n1[k] == 16 * P.midnt && n2[k] == 16 * P.midnt;
     P.nr0 = P.nruns;
     if (P.fuse) {
         P.nr0 = (P.mid0 + KS_L - 1) / KS_L;

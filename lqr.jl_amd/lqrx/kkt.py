@@ -107,7 +107,8 @@ def random_kkt(st: KktStructure, batch: int, seed: int, h_mode: int = H_DIAG, dy
     condition / goal rows are [I 0]); H_k SPD (diagonal, block-diagonal or dense).
     dyn "small": A = I + 0.1·G, B = 0.1·G (the small shapes); "dense": the SURVEY §8(d)
     random-dense scaling A = I + (0.1/√n)·G, B = G/√n, which keeps large n (cfg5's 64)
-    well conditioned."""
+    well conditioned.  D2 and the boundary stage rows are structural identities here; inputs with
+    every row random, on any per-knot structure, are tests/kkt_general.py's general_kkt."""
     rng = np.random.default_rng(seed)
     n, m, N = st.n, st.m, st.N
     sY, sy, sH, sg = st.sizes(h_mode)

@@ -284,11 +284,28 @@ class KktStructure:
         self.n1 = np.array([0] + [n] * (N - 1), np.int32)
         self.n2 = np.array([n] * (N - 1) + [0], np.int32)
         self.w = np.array([n + m] * (N - 1) + [n], np.int32)
+        self._derive()
+
+    def _derive(self):
         self.rows = self.n1 + self.p + self.n2
         self.sY = int(np.sum(self.rows * self.w))
         self.sy = int(np.sum(self.p + self.n2))
         self.sg = int(np.sum(self.w))
         self.P = self.sy
+
+    @classmethod
+    def from_blocks(cls, n1, p, n2, w):
+        """Any structure the C side takes: the four per-knot arrays as given (n1[0] = 0,
+        n1[k] = n2[k−1], n2[N−1] = 0).  n and m have no meaning here and are None."""
+        st = cls.__new__(cls)
+        st.n1, st.p, st.n2, st.w = (np.ascontiguousarray(a, dtype=np.int32) for a in (n1, p, n2, w))
+        st.N = len(st.w)
+        if not (len(st.n1) == len(st.p) == len(st.n2) == st.N and st.n1[0] == 0 and st.n2[-1] == 0
+                and (st.n1[1:] == st.n2[:-1]).all()):
+            raise ValueError("need n1[0] = 0, n1[k] = n2[k-1], n2[N-1] = 0 and four arrays of one length")
+        st.n = st.m = None
+        st._derive()
+        return st
 
     def sH(self, h_mode):
         return self.sg if h_mode == 2 else int(np.sum(self.w * self.w))

@@ -727,6 +727,10 @@ int lqrx_kkt_solve_host_devices(const lqrx_kkt_desc *desc, const void *Y, const 
  *   iters  int32·batch out: accepted steps
  *   status int32·batch out: 0 converged (‖c‖∞ < tol_p and ‖∇f+∇cᵀλ‖₂ < tol_d before a
  *          step), 1 max_iters reached, 2 line search failed (iterate left unchanged)
+ * Validation (-1): beside the ranges noted at the fields, a problem with more constraint rows
+ * than variables, N·nx + (N−1)·nu < nx·(N+1) + stage_rows·(N−2), is rejected — its Newton
+ * KKT matrix is singular at every point (the reference raises PosDefException).  That rules
+ * out a stage row on the cartpole or DoubleIntegrator(1), Dubins with N = 2, cartpole with N < 5.
  * ------------------------------------------------------------------------------------ */
 enum {
     LQRX_MODEL_DUBINS = 0,

@@ -1868,6 +1868,12 @@ int validate_sqp(const lqrx_sqp_desc *d, int *nx, int *nu)
                 return set_err(-1, "desc.params (mc, mp, l, g) must be positive and finite");
     if (!(d->mu >= 0) || !(d->tol_p >= 0) || !(d->tol_d >= 0))
         return set_err(-1, "desc.mu / tol_p / tol_d must be >= 0");
+    // more constraint rows than variables: the Newton KKT matrix is singular at every point
+    const int64_t nvar = (int64_t)d->N * *nx + (int64_t)(d->N - 1) * *nu,
+                  ncon = (int64_t)(d->N + 1) * *nx + (int64_t)(d->N - 2) * d->stage_rows;
+    if (nvar < ncon)
+        return set_err(-1, "over-constrained: %lld variables (N*nx + (N-1)*nu) < %lld constraint rows "
+                           "(nx*(N+1) + stage_rows*(N-2))", (long long)nvar, (long long)ncon);
     return 0;
 }
 

@@ -199,17 +199,22 @@ class TrajSQP:
         A = self.jac(z)
         return -A.T @ np.linalg.solve(A @ A.T, self.c(z + dz))
 
-    def line_search(self, z, dz):
-        """dubins_sqp.jl:74-97.  Returns (z_new, accepted, alpha, used_soc)."""
+    def line_search(self, z, dz, trace=None):
+        """dubins_sqp.jl:74-97.  Returns (z_new, accepted, alpha, used_soc).  With a `trace`
+        (new_trace()) every comparison made is recorded with its relative margin."""
         phi0 = self.phi(z)
         dphi = self.grad(z) @ dz - self.mu * np.abs(self.c(z)).sum()
         a = 1.0
         for _ in range(LS_TRIES):
-            if self.phi(z + a * dz) <= phi0 + ETA * a * dphi:
+            lhs, rhs = self.phi(z + a * dz), phi0 + ETA * a * dphi
+            _margin(trace, "armijo" if a == 1.0 else "backtrack", lhs, rhs)
+            if lhs <= rhs:
                 return z + a * dz, True, a, False
             if a == 1.0:
                 dzh = self.soc(z, dz)
-                if self.phi(z + dz + dzh) < phi0 + ETA * dphi:
+                lhs, rhs = self.phi(z + dz + dzh), phi0 + ETA * dphi
+                _margin(trace, "soc", lhs, rhs)
+                if lhs < rhs:
                     return z + dz + dzh, True, a, True
             a *= RHO
         return z, False, 0.0, False
@@ -257,23 +262,48 @@ def double_integrator_problem(D=3, N=101, mu=1.0, seed=1, x0=None, xf=None):
     return prob, np.zeros(prob.NN)
 
 
-def solve(prob: TrajSQP, z0, iters=10, tol_p=1e-5, tol_d=1e-5):
+def new_trace():
+    """An empty trace for solve / line_search: `margins` gets one (step, kind, margin) per
+    comparison the loop makes — kind tol_p, tol_d (convergence check; tol_d only when the primal
+    test passed, as `and` evaluates it), armijo (α = 1), soc, backtrack; margin = |lhs − rhs| /
+    max(|lhs|, |rhs|), the relative distance of the two sides, so a small value marks a decision
+    that rounding could flip — `lam` the multipliers of every accepted step (lam[i] belongs to
+    hist[i + 1]) and `alpha` its step length."""
+    return dict(margins=[], lam=[], alpha=[])
+
+
+def _margin(trace, kind, lhs, rhs):
+    if trace is not None:
+        den = max(abs(lhs), abs(rhs))
+        trace["margins"].append((trace.get("step", 0), kind, abs(lhs - rhs) / den if den > 0 else 0.0))
+
+
+def solve(prob: TrajSQP, z0, iters=10, tol_p=1e-5, tol_d=1e-5, trace=None):
     """CholeskySolver.solve! loop (cholesky_solver.jl:109-153).  Returns dict z, lam, iters
     (steps taken), status (0 converged, 1 iteration limit, 2 line search failed), hist
-    (iterates), soc (per step: second-order correction used)."""
+    (iterates), soc (per step: second-order correction used).  `trace` (new_trace()) records
+    the decision margins and the per-step multipliers; the result is the same with or without."""
     z, lam = np.array(z0, float), np.zeros(prob.P)
     hist, socs = [z.copy()], []
     for it in range(iters):
+        if trace is not None:
+            trace["step"] = it
         fp, fd = prob.residuals(z, lam)
+        _margin(trace, "tol_p", fp, tol_p)
+        if fp < tol_p:
+            _margin(trace, "tol_d", fd, tol_d)
         if fp < tol_p and fd < tol_d:
             return dict(z=z, lam=lam, iters=it, status=0, hist=hist, soc=socs)
         dz, lam_n = prob.newton(z)
-        z_n, ok, _, used = prob.line_search(z, dz)
+        z_n, ok, alpha, used = prob.line_search(z, dz, trace)
         if not ok:
             return dict(z=z, lam=lam, iters=it, status=2, hist=hist, soc=socs)
         z, lam = z_n, lam_n
         hist.append(z.copy())
         socs.append(used)
+        if trace is not None:
+            trace["lam"].append(lam.copy())
+            trace["alpha"].append(alpha)
     return dict(z=z, lam=lam, iters=iters, status=1, hist=hist, soc=socs)
 
 

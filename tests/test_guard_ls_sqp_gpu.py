@@ -19,7 +19,9 @@ profiles/r08/guards/guard_gpu_tests.log: the four test_guard_*_gpu.py files toge
 No guard was touched and no output element was left unwritten; Ā's block upper triangle comes back as
 written zeros, as buildAb! leaves it.  Worst error against the oracles: LS U, X 5.1e-16 at (2, 1, 2),
 2.0e-13 at (3, 2, 5), 3.1e-13 at (2, 2, 98); SQP z, λ Dubins 6.3e-15 (10 steps), cartpole 1.3e-13
-(4–5 steps), DoubleIntegrator(3) 2.5e-14 (1 step).
+(4–5 steps), DoubleIntegrator(3) 2.5e-14 (1 step).  The three cases from tests/sqp_cases.py (padded
+KKT bin, large-block KKT kernels), in a later run: no guard touched; Dubins with a stage row 1.3e-12,
+DoubleIntegrator(1) 2.5e-15, DoubleIntegrator(3) with two stage rows 9.7e-12.
 """
 import numpy as np
 import pytest
@@ -119,12 +121,21 @@ def _sqp_cases():
         prob, probs, Z0, x0, xf = _double_integrator(3, 5, 10.0, 5, 3)
         return prob, probs, Z0, x0, xf, 1e-8
 
-    return dict(dubins=dubins, cartpole=cartpole, di3=di3)
+    def matrix(name):
+        """a case of tests/sqp_cases.py: the padded-bin and whole-batch KKT routes' scratch carving"""
+        import sqp_cases as C
+
+        return lambda: (*C.case(name), C.tol(name))
+
+    return dict(dubins=dubins, cartpole=cartpole, di3=di3, dubins_pk1=matrix("dubins_pk1_N4"),
+                di1_pk0=matrix("di1_pk0_N4"), di3_pk2=matrix("di3_pk2_N8"))
 
 
-@pytest.mark.parametrize("model", ["dubins", "cartpole", "di3"])
+@pytest.mark.parametrize("model", ["dubins", "cartpole", "di3", "dubins_pk1", "di1_pk0", "di3_pk2"])
 def test_sqp_solve_touches_only_its_buffers(lqrx, gpu_ok, model):
-    """Dubins N = 4, cartpole N = 6, DoubleIntegrator(3) N = 5 with its stage row; batch 3."""
+    """Dubins N = 4, cartpole N = 6, DoubleIntegrator(3) N = 5 with its stage row; Dubins N = 4 with a
+    stage row and DoubleIntegrator(1) N = 4 (padded KKT bin), DoubleIntegrator(3) N = 8 with two stage
+    rows (large-block KKT kernels, whole batch); batch 3."""
     import torch
     import lqrx.sqp as Q
 
@@ -160,7 +171,7 @@ def test_sqp_solve_touches_only_its_buffers(lqrx, gpu_ok, model):
     status = plain["status"].cpu().numpy()
     worst = 0.0
     for b in range(bt):
-        r = S.solve(probs[b], Z0[b])
+        r = S.solve(probs[b], Z0[b], iters=prob.max_iters, tol_p=prob.tol_p, tol_d=prob.tol_d)   # the defaults, or the case's
         assert status[b] == r["status"] and iters[b] == r["iters"], (b, status[b], r["status"], iters[b], r["iters"])
         ez = np.abs(z[b] - r["z"]).max() / np.abs(r["z"]).max()
         el = np.abs(lam[b] - r["lam"]).max() / max(np.abs(r["lam"]).max(), 1e-300) if r["iters"] else 0.0

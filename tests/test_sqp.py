@@ -96,6 +96,20 @@ def test_sqp_desc_validation(lqrx):
     d = Q.DoubleIntegratorSQP(3, 11).desc(2)
     d.stage_A[0] = float("nan")
     assert lib.lqrx_sqp_solve(C.byref(d), *([None] * 6), None) == -1
+    # over-constrained (more constraint rows than variables: a singular Newton KKT) is refused …
+    from dataclasses import replace
+    over = [replace(Q.CartpoleSQP(11), stage_A=(1.0, 0.0, 0.0, 0.0), stage_b=(0.1,)),     # cartpole + a stage row
+            replace(Q.DoubleIntegratorSQP(1, 11, stage_A=np.ones((1, 2))), stage_b=(0.1,)),  # DI(1) + a stage row
+            Q.DubinsSQP(2, 0.3),
+            Q.CartpoleSQP(4)]
+    for pr in over:
+        assert lib.lqrx_sqp_solve(C.byref(pr.desc(2)), *([None] * 6), None) == -1, pr
+        assert b"over-constrained" in lib.lqrx_last_error()
+        assert lib.lqrx_sqp_solve_host(C.byref(pr.desc(2)), *([None] * 6)) == -1, pr
+    # … and the square / smallest well-posed problems still pass (batch 0: nothing launches)
+    for pr in (Q.DubinsSQP(3, 0.3), Q.CartpoleSQP(5),
+               replace(Q.DubinsSQP(3, 0.3), stage_A=(1.0, -1.0, 0.0), stage_b=(0.1,))):
+        assert lib.lqrx_sqp_solve(C.byref(pr.desc(0)), *([None] * 6), None) == 0, pr
     nx, nu = C.c_int32(), C.c_int32()
     assert lib.lqrx_sqp_model_dims(1, C.byref(nx), C.byref(nu)) == 0 and (nx.value, nu.value) == (4, 1)
     assert lib.lqrx_sqp_model_dims(0, C.byref(nx), C.byref(nu)) == 0 and (nx.value, nu.value) == (3, 2)
